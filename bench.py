@@ -20,6 +20,12 @@ states the mode that actually ran (SEA_GEMM_TERMS / SEA_GEMM_TERMS_BWD select ot
 with no collective in the loop (weak scaling).  After the timed window `--sustain` further steps (default 300 = a
 full SEA attack's length) are timed the same way and reported as `config.sustained_ms_per_step`: the chip lowers
 its clock under sustained matrix load, which a 20-step window does not see.
+
+`--dump-outputs DIR` writes what the last timed step left for a caller of the loop (rank 0's images) as DIR/<name>.npy,
+float32 / float64, ~59 MB: the attack's result `x_best_adv` in full, every other array of more than 2**21 elements at 2**21
+fixed, seeded positions (see `dump_outputs`).  The inputs depend on the arguments only, and the convolutions left to MIOpen
+run in immediate mode (a fixed solver, not the fastest of a timed search), so runs repeat bit for bit and two builds can be
+compared output for output.
 """
 import argparse
 import json
@@ -303,6 +309,41 @@ def strict_fp32_ms(A, N, run, model, x, y, eps, args, C, weights, barrier):
         A.release_graph_cache(model)
 
 
+DUMP_SAMPLE = 2 ** 21       # elements kept of an array dumped as a sample (--dump-outputs)
+DUMP_SEED = 0
+
+
+def snapshot_outputs(run, i):
+    """Copies (on the device) of what ``run.step(i)`` leaves a caller: the attack's state after the step -- ``result()``, the
+    iterate it evaluated, that iterate's input gradient and argmax, its per-image tracking loss and the step size K7 set.  Taken
+    right after the timed window: the sustained window goes on stepping the same run."""
+    x_best, acc, loss_best, x_best_adv = run.result()
+    return {"x_best_adv": x_best_adv.clone(), "x_best": x_best.clone(), "x_adv": run.x_adv.clone(), "grad": run.grad.clone(),
+            "pred": run.pred.clone(), "acc": acc.clone(), "loss_best": loss_best.clone(),
+            "track_loss": run.st.loss_steps[i].clone(), "step_size": run.st.step.clone()}
+
+
+def dump_outputs(snap, out_dir):
+    """DIR/<name>.npy per array: float32 for float32 data and 8 / 16-bit integers, float64 for wider integers (exact).
+    `x_best_adv` in full; every other array of more than DUMP_SAMPLE elements as its flattened elements at DUMP_SAMPLE
+    positions drawn without replacement by torch.randperm(numel, Generator.manual_seed(DUMP_SEED)) and sorted (the same
+    positions for the same shape).  At most 64 MB in all."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in snap.items():
+        t = t.detach().cpu()
+        t = t.float() if (t.is_floating_point() or t.element_size() <= 2) else t.double()
+        if name != "x_best_adv" and t.numel() > DUMP_SAMPLE:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(DUMP_SEED))[:DUMP_SAMPLE].sort().values
+            t = t.reshape(-1)[idx]
+        a = t.numpy()
+        total += a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    assert total <= 64 * 10 ** 6, f"--dump-outputs wrote {total} bytes"
+    return total
+
+
 def _mode_name(terms):
     return {22: "fp16x2 (22 significant bits per operand, 3 MFMA products)", 3: "bf16x3 (24 bits, 6 products)",
             2: "bf16x2 (16 bits, 3 products)"}.get(terms, "hipBLASLt fp32")
@@ -381,7 +422,11 @@ def main():
                     help="force K2u (loss fused with the model's final bilinear upsample); default: the library's "
                          "heuristic (unfused unless the full-resolution logits + gradient exceed 24 GB)")
     ap.add_argument("--no-fuse-upsample", action="store_true", help="force the model's own upsample + K2")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy (float32 / float64, <= 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -404,7 +449,13 @@ def main():
         world = int(one.item())
     if args.gpus != world and rank == 0:
         print(f"[bench] note: --gpus {args.gpus} but {world} rank(s) are running; reporting n_gpus={world}", file=sys.stderr)
-    torch.backends.cudnn.benchmark = True  # MIOpen find mode: pick the fastest conv algorithms
+    # Convolutions left to MIOpen (the stem's second conv, forward and input gradient) run in immediate mode with the
+    # find-db off: the solver is a fixed function of shape, device and MIOpen version.  Find mode times the solvers and keeps
+    # the fastest, so the solver -- and the rounding -- changed from run to run and box to box, and the backward solver it
+    # picked was not bitwise repeatable either; APGD's sign steps carry such a difference into the iterates.
+    os.environ.setdefault("MIOPEN_DEBUG_DISABLE_FIND_DB", "1")
+    torch.backends.cudnn.benchmark = False
+    torch.backends.miopen.immediate = True
 
     from semseg import _native as N, attacker as A
     from semseg.models.convnext_upernet import GEMM_TERMS, _bwd_terms
@@ -443,6 +494,7 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     gc.enable()
+    snap = snapshot_outputs(run, W + K - 1) if (args.dump_outputs and rank == 0) else None
     per_rank = None
     if world > 1:
         # max over ranks is the job's time; the per-rank rows say which rank (and whether its host) set it
@@ -547,6 +599,8 @@ def main():
         }
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(C, args.backbone)
+        if snap is not None:
+            dump_outputs(snap, args.dump_outputs)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()  # rank 0 measured the ceilings after the timed region
