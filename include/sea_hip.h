@@ -567,6 +567,23 @@ int sea_gemm_split_pipeline(int pipe);
 int sea_probe_stream_copy(const void* src, void* dst, size_t bytes, int non_temporal, void* stream);
 int sea_probe_stream_read(const void* src, float* sink, size_t bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * K10 multi-scale + flip evaluation (semseg.val.evaluate_msf), replacing the per-(scale, flip) ATen sequence of
+ * semseg/val.py:340-365: interpolate(images, align_corners=True) [+ flip] -> model -> [flip] -> interpolate(logits,
+ * (H, W), align_corners=True) -> softmax(dim=1) -> scaled_logits +=.
+ * sea_msf_resize_input: x (planes, h, w) -> y and/or y_flip (planes, H, W), bilinear align_corners=True (ATen's fp32
+ *   arithmetic); y_flip is the same image mirrored along W.  Either output may be NULL, not both.  Up or down.
+ * sea_msf_accumulate: score (B, C, H, W) += softmax over C of the align_corners=True resize to (H, W) of the logits of
+ *   one scaled forward, mirrored back along W when flip != 0.  logits (B, C, hl, wl): hl == Hs and wl == Ws = the model's
+ *   output at the scaled size (Hs, Ws); smaller = its forward_lowres output, up-sampled to (Hs, Ws) on the fly with
+ *   M2's align_corners=False rule (the scaled-size logits are never written).  C <= SEA_MSF_MAX_CLASSES, hl <= Hs,
+ *   wl <= Ws, H*W and Hs*Ws < 2^31.  No atomics: bitwise reproducible.  score must not alias logits. */
+#define SEA_MSF_MAX_CLASSES 192
+int sea_msf_resize_input(const float* x, float* y, float* y_flip, int64_t planes, int h, int w, int H, int W,
+                         void* stream);
+int sea_msf_accumulate(const float* logits, float* score, int B, int C, int hl, int wl, int Hs, int Ws, int H, int W,
+                       int flip, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

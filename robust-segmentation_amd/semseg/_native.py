@@ -112,6 +112,8 @@ _SIGS = {
     "sea_gemm_split_pipeline": (_i, [_i]),
     "sea_probe_stream_copy": (_i, [_vp, _vp, _sz, _i, _vp]),
     "sea_probe_stream_read": (_i, [_vp, _vp, _sz, _vp]),
+    "sea_msf_resize_input": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "sea_msf_accumulate": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -348,6 +350,61 @@ def confusion(pred, y, n_cls: int, hist=None):
     _check(lib().sea_confusion(_p(pred.contiguous()), int_bytes(pred), _p(y.contiguous()), int_bytes(y), pred.numel(),
                                n_cls, _p(hist), _stream()), "sea_confusion")
     return hist
+
+
+# ------------------------------------------------------------------------------------------------ K10
+MSF_MAX_CLASSES = 192     # SEA_MSF_MAX_CLASSES
+
+
+def msf_resize_input(x, size, flip: bool = False, plain: bool = True, out=None, out_flip=None):
+    """F.interpolate(x, size, mode="bilinear", align_corners=True) of an fp32 NCHW device batch and/or the same result
+    mirrored along W (torch.flip(dims=(3,))), in one pass.  Returns (plain or None, flipped or None)."""
+    _dev(x, out, out_flip)
+    x = _f32c(x)
+    if x.dim() != 4:
+        raise SeaNativeError(f"msf_resize_input: expected (B, C, h, w), got {tuple(x.shape)}")
+    B, Cc, h, w = x.shape
+    H, W = int(size[0]), int(size[1])
+    if not (plain or flip) or H <= 0 or W <= 0:
+        raise SeaNativeError("msf_resize_input: nothing to write")
+    shape = (B, Cc, H, W)
+
+    def _buf(t, want):
+        if not want:
+            return None
+        if t is None:
+            return torch.empty(shape, dtype=torch.float32, device=x.device)
+        if tuple(t.shape) != shape:
+            raise SeaNativeError(f"msf_resize_input: output shape {tuple(t.shape)} != {shape}")
+        return _f32c(t)
+
+    y, yf = _buf(out, plain), _buf(out_flip, flip)
+    _check(lib().sea_msf_resize_input(_p(x), _p(y), _p(yf), B * Cc, h, w, H, W, _stream()), "sea_msf_resize_input")
+    return y, yf
+
+
+def msf_accumulate(logits, score, scaled_size, flip: bool = False):
+    """score (B, C, H, W) += softmax_C(F.interpolate(flip?(up(logits)), (H, W), "bilinear", align_corners=True)), flipped
+    back along W first when ``flip``.  ``logits``: the model's output at ``scaled_size`` (Hs, Ws), or its ``forward_lowres``
+    output (smaller), which is up-sampled to the scaled size on the fly with the model's align_corners=False rule."""
+    _dev(logits, score)
+    logits, score = _f32c(logits), _f32c(score)
+    if logits.dim() != 4 or score.dim() != 4:
+        raise SeaNativeError("msf_accumulate: logits and score must be (B, C, h, w) / (B, C, H, W)")
+    B, Cc, hl, wl = logits.shape
+    Hs, Ws = int(scaled_size[0]), int(scaled_size[1])
+    if score.shape[0] != B or score.shape[1] != Cc:
+        raise SeaNativeError(f"msf_accumulate: score {tuple(score.shape)} does not match logits {tuple(logits.shape)}")
+    if Cc > MSF_MAX_CLASSES:
+        raise SeaNativeError(f"msf_accumulate: {Cc} classes > {MSF_MAX_CLASSES}")
+    if hl > Hs or wl > Ws:
+        raise SeaNativeError(f"msf_accumulate: logits {hl}x{wl} larger than the scaled size {Hs}x{Ws}")
+    if score.data_ptr() == logits.data_ptr():
+        raise SeaNativeError("msf_accumulate: score aliases logits")
+    H, W = score.shape[2:]
+    _check(lib().sea_msf_accumulate(_p(logits), _p(score), B, Cc, hl, wl, Hs, Ws, H, W, int(bool(flip)), _stream()),
+           "sea_msf_accumulate")
+    return score
 
 
 def count_ignored(y, out=None):
