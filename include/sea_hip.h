@@ -584,6 +584,34 @@ int sea_msf_resize_input(const float* x, float* y, float* y_flip, int64_t planes
 int sea_msf_accumulate(const float* logits, float* score, int B, int C, int hl, int wl, int Hs, int Ws, int H, int W,
                        int flip, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * P1-P3: PSPNet-ResNet50 (semseg/models/ddcat_psp.py:372-486 with backbones/resnet_ddcat.py), the steps of its frozen
+ * eval forward / input gradient that are not convolutions.  All fp32.
+ * sea_psp_polyphase_split: x dense NHWC (B, H, W, C) -> y (B*P, ceil(H/d), ceil(W/d), C), P = d*d (first_only: P = 1,
+ *   phase (0, 0) only), y[b*P + py*d + px][m][n] = x[b][py + d m][px + d n], 0 where that lies outside x.  Replaces the
+ *   dilated 3x3 convolutions of layer3 / layer4 (ddcat_psp.py:429-438: dilation 2 / 4, padding = dilation) by ordinary
+ *   3x3 convolutions of the sub-images (the zero tails are the zero padding), and, first_only with d = 2, the stride-2
+ *   sampling of layer2's 1x1 downsample (resnet_ddcat.py:149-156).
+ * sea_psp_polyphase_merge: the inverse on the valid positions (tails cropped) = the adjoint of the split; with
+ *   first_only, x is zero off the phase-(0, 0) grid.  C % 4 == 0, 16-byte aligned, x != y.
+ * sea_psp_upsample_ac: F.interpolate(x, (H, W), mode="bilinear", align_corners=True) of planes (h, w) -> (H, W), NCHW,
+ *   ATen's arithmetic and evaluation order (the final logits, ddcat_psp.py:466-467).
+ * sea_psp_upsample_ac_bwd: its input gradient by a two-pass separable gather (work: planes*H*w floats), no atomics.
+ * sea_psp_upsample_ac_nhwc / _bwd: the same for a dense NHWC (B, h, w, C) input and an output (or output gradient) with
+ *   pixel stride S >= C: a channel slice of the PPM's concatenation (ddcat_psp.py:23-30).  work: B*H*w*C floats.
+ * sea_psp_add_relu: y = max(a + r, 0) (the bottleneck's out += residual; relu(out), resnet_ddcat.py:102-105).
+ * sea_psp_add_relu_bwd: gx = y > 0 ? gy : 0 (the gradient of both a and r).  n % 4 == 0, 16-byte aligned. */
+int sea_psp_polyphase_split(const float* x, float* y, int B, int H, int W, int C, int d, int first_only, void* stream);
+int sea_psp_polyphase_merge(const float* y, float* x, int B, int H, int W, int C, int d, int first_only, void* stream);
+int sea_psp_upsample_ac(const float* x, float* y, int64_t planes, int h, int w, int H, int W, void* stream);
+int sea_psp_upsample_ac_bwd(const float* gy, float* gx, float* work, int64_t planes, int h, int w, int H, int W,
+                            void* stream);
+int sea_psp_upsample_ac_nhwc(const float* x, float* y, int B, int C, int h, int w, int H, int W, int S, void* stream);
+int sea_psp_upsample_ac_nhwc_bwd(const float* gy, float* gx, float* work, int B, int C, int h, int w, int H, int W,
+                                 int S, void* stream);
+int sea_psp_add_relu(const float* a, const float* r, float* y, int64_t n, void* stream);
+int sea_psp_add_relu_bwd(const float* gy, const float* y, float* gx, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

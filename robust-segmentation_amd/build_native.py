@@ -49,6 +49,7 @@ SOURCES = [
     ("mlp_fused.hip", ["-fno-slp-vectorize"]),
     ("classifier.hip", []),
     ("msf_kernels.hip", ["-ffp-contract=off"]),
+    ("psp_kernels.hip", []),
     ("greedy_host.cpp", ["-ffp-contract=off"]),
     ("api_misc.cpp", []),
 ]

@@ -114,6 +114,14 @@ _SIGS = {
     "sea_probe_stream_read": (_i, [_vp, _vp, _sz, _vp]),
     "sea_msf_resize_input": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "sea_msf_accumulate": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "sea_psp_polyphase_split": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "sea_psp_polyphase_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "sea_psp_upsample_ac": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "sea_psp_upsample_ac_bwd": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "sea_psp_upsample_ac_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "sea_psp_upsample_ac_nhwc_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "sea_psp_add_relu": (_i, [_vp, _vp, _vp, _i64, _vp]),
+    "sea_psp_add_relu_bwd": (_i, [_vp, _vp, _vp, _i64, _vp]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -405,6 +413,124 @@ def msf_accumulate(logits, score, scaled_size, flip: bool = False):
     _check(lib().sea_msf_accumulate(_p(logits), _p(score), B, Cc, hl, wl, Hs, Ws, H, W, int(bool(flip)), _stream()),
            "sea_msf_accumulate")
     return score
+
+
+# ------------------------------------------------------------------------------------------------ P1-P3 (PSPNet)
+def _psp_cl(t, what):
+    if t.dtype != torch.float32 or cl_pixel_stride(t) != t.shape[1]:
+        raise SeaNativeError(f"{what}: dense channels_last float32 (B,C,H,W) with C % 4 == 0 expected")
+    return t
+
+
+def polyphase_split(x, d: int, first_only: bool = False):
+    """P1: the d*d polyphase sub-images of a dense channels_last (B,C,H,W) tensor as one channels_last batch
+    (B*d*d, C, ceil(H/d), ceil(W/d)), image-major, phase (py, px) at py*d + px; zero past the image.  ``first_only``:
+    phase (0, 0) alone, (B, C, ceil(H/d), ceil(W/d)) = x[:, :, ::d, ::d]."""
+    _dev(x)
+    _psp_cl(x, "polyphase_split")
+    B, Cc, H, W = x.shape
+    Hs, Ws, P = -(-H // d), -(-W // d), 1 if first_only else d * d
+    y = _empty_cl(B * P, Cc, Hs, Ws, x.device)
+    _check(lib().sea_psp_polyphase_split(_p(x), _p(y), B, H, W, Cc, int(d), int(bool(first_only)), _stream()),
+           "sea_psp_polyphase_split")
+    return y
+
+
+def polyphase_merge(y, size, d: int, first_only: bool = False):
+    """P1: the inverse (and adjoint) of ``polyphase_split``: (B*P, C, Hs, Ws) channels_last -> (B, C, H, W) channels_last,
+    ``size`` = (H, W); the zero tails are cropped; with ``first_only`` every position off the phase-(0, 0) grid is 0."""
+    _dev(y)
+    _psp_cl(y, "polyphase_merge")
+    H, W = int(size[0]), int(size[1])
+    P = 1 if first_only else d * d
+    Bp, Cc, Hs, Ws = y.shape
+    if Bp % P or Hs != -(-H // d) or Ws != -(-W // d):
+        raise SeaNativeError(f"polyphase_merge: {tuple(y.shape)} is not a d={d} split of {H}x{W}")
+    x = _empty_cl(Bp // P, Cc, H, W, y.device)
+    _check(lib().sea_psp_polyphase_merge(_p(y), _p(x), Bp // P, H, W, Cc, int(d), int(bool(first_only)), _stream()),
+           "sea_psp_polyphase_merge")
+    return x
+
+
+def upsample_ac(x, size):
+    """P2: F.interpolate(x, size, mode="bilinear", align_corners=True) of a contiguous fp32 NCHW device tensor"""
+    _dev(x)
+    x = _f32c(x)
+    B, Cc, h, w = x.shape
+    H, W = int(size[0]), int(size[1])
+    y = torch.empty(B, Cc, H, W, dtype=torch.float32, device=x.device)
+    _check(lib().sea_psp_upsample_ac(_p(x), _p(y), B * Cc, h, w, H, W, _stream()), "sea_psp_upsample_ac")
+    return y
+
+
+def upsample_ac_backward(gy, in_size):
+    """P2: input gradient of ``upsample_ac`` (deterministic gather)"""
+    _dev(gy)
+    gy = _f32c(gy)
+    B, Cc, H, W = gy.shape
+    h, w = int(in_size[0]), int(in_size[1])
+    gx = torch.empty(B, Cc, h, w, dtype=torch.float32, device=gy.device)
+    work = torch.empty(B * Cc * H * w, dtype=torch.float32, device=gy.device)
+    _check(lib().sea_psp_upsample_ac_bwd(_p(gy), _p(gx), _p(work), B * Cc, h, w, H, W, _stream()),
+           "sea_psp_upsample_ac_bwd")
+    return gx
+
+
+def upsample_ac_cl(x, size, out=None):
+    """P2: the align_corners=True up-sampling of a dense channels_last (B,C,h,w) tensor; ``out``: a (B,C,H,W) channels_last
+    tensor or a channel slice of a wider one (written in place)."""
+    _dev(x, out)
+    _psp_cl(x, "upsample_ac_cl")
+    B, Cc, h, w = x.shape
+    H, W = int(size[0]), int(size[1])
+    if out is None:
+        out = _empty_cl(B, Cc, H, W, x.device)
+    S = cl_pixel_stride(out)
+    if tuple(out.shape) != (B, Cc, H, W) or S is None:
+        raise SeaNativeError("upsample_ac_cl: out must be a (B,C,H,W) channels_last tensor or a channel slice of one")
+    _check(lib().sea_psp_upsample_ac_nhwc(_p(x), _p(out), B, Cc, h, w, H, W, S, _stream()), "sea_psp_upsample_ac_nhwc")
+    return out
+
+
+def upsample_ac_cl_backward(gy, in_size):
+    """P2: input gradient (dense channels_last (B,C,h,w)) of ``upsample_ac_cl``; gy channels_last or a channel slice"""
+    _dev(gy)
+    S = cl_pixel_stride(gy)
+    if S is None:
+        raise SeaNativeError("upsample_ac_cl_backward: channels_last float32 tensor (or channel slice) with C % 4 == 0 expected")
+    B, Cc, H, W = gy.shape
+    h, w = int(in_size[0]), int(in_size[1])
+    gx = _empty_cl(B, Cc, h, w, gy.device)
+    work = torch.empty(B * H * w * Cc, dtype=torch.float32, device=gy.device)
+    _check(lib().sea_psp_upsample_ac_nhwc_bwd(_p(gy), _p(gx), _p(work), B, Cc, h, w, H, W, S, _stream()),
+           "sea_psp_upsample_ac_nhwc_bwd")
+    return gx
+
+
+def _same_dense(a, b):
+    """a and b have the same shape and the same dense memory order (NCHW- or channels_last-contiguous)"""
+    return (a.shape == b.shape and a.stride() == b.stride() and a.dtype == torch.float32 and b.dtype == torch.float32
+            and (a.is_contiguous() or a.is_contiguous(memory_format=torch.channels_last)))
+
+
+def add_relu(a, r):
+    """P3: max(a + r, 0) of two float32 tensors of the same shape and dense layout (the result keeps that layout)"""
+    _dev(a, r)
+    if not _same_dense(a, r) or a.numel() % 4:
+        raise SeaNativeError("add_relu: same-shape, same-layout dense float32 tensors with numel % 4 == 0 expected")
+    y = torch.empty_like(a)
+    _check(lib().sea_psp_add_relu(_p(a), _p(r), _p(y), a.numel(), _stream()), "sea_psp_add_relu")
+    return y
+
+
+def add_relu_backward(gy, y):
+    """P3: gy where y > 0, else 0 (the gradient of both addends of ``add_relu``)"""
+    _dev(gy, y)
+    if not _same_dense(gy, y) or y.numel() % 4:
+        raise SeaNativeError("add_relu_backward: gy must match y's shape and layout")
+    gx = torch.empty_like(y)
+    _check(lib().sea_psp_add_relu_bwd(_p(gy), _p(y), _p(gx), y.numel(), _stream()), "sea_psp_add_relu_bwd")
+    return gx
 
 
 def count_ignored(y, out=None):

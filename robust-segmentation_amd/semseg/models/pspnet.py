@@ -1,0 +1,369 @@
+"""PSPNet-ResNet50 (semseg/models/ddcat_psp.py:372-486 of the reference, with the ``clean=True`` deep-base ResNet-50 of
+backbones/resnet_ddcat.py:110-131): the VOC model of the reference's tools/infer.py (``eval(MODEL.NAME)(50, N_CLS)``,
+configs/voc_pspnet_cais.yaml) and the architecture of the DDC-AT / CAIS baselines.
+
+Same modules, names and state-dict keys as the reference (370 keys, ``aux.*`` included), so a reference checkpoint loads
+with ``strict=True``.  Training mode (and ``indicate == 1``) runs the reference's forward on plain torch ops.  The frozen
+eval forward of a float32 device batch -- what SEA attacks -- and its input gradient run on the device kernels
+("PSPNet"):
+
+- 1x1 convolutions (stride 1): M8 with the eval BatchNorm folded in (``_PointwiseRelu`` / ``_linear_frozen``);
+- 3x3 stride-1 convolutions: the F(4x4,3x3) Winograd path (M1) with BatchNorm + ReLU in its epilogue;
+- the dilated 3x3 convolutions of layer3 / layer4: P1 polyphase split -> Winograd on the d*d sub-images -> P1 merge;
+- layer2's stride-2 1x1 downsample: P1 phase (0, 0), then M8;
+- the bottleneck's ``relu(bn3(conv3(.)) + identity)``: M8 with the folded bias, then P3;
+- PPM: the adaptive pool of M2'', M8, and P2 writing the align_corners=True up-sampling straight into the concatenation;
+- ``cls``: Winograd 4096 -> 512, then the M10 classifier GEMM (NCHW logits), then P2 (x8, align_corners=True).
+The stem's stride-2 3-input-channel convolution, layer2's stride-2 3x3 and the max-pool stay with the library (about 1 %
+of the FLOPs).  There is deliberately no ``forward_lowres`` hook: K2u and K10b assume align_corners=False.
+
+``USE_NATIVE = False`` runs the plain torch forward in eval mode too (A/B runs, the stock yardstick of the tests)."""
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import convnext_upernet as _M       # WINOGRAD_TILE / WINOGRAD_MIN_PIXELS are read from there at call time
+from .convnext_upernet import (_PointwiseRelu, _WinoConv3x3, _classify, _adaptive_pool, _dense_cl, _folded_bn, _fp32_bwd,
+                               _fp32_fwd, _linear_frozen, _split_ok, _stable, _tkey, _wino_ok)
+
+USE_NATIVE = True
+_CL = torch.channels_last
+
+
+# ---------------------------------------------------------------------------------------------------- modules
+class Bottleneck(nn.Module):
+    """resnet_ddcat.py:70-107"""
+    expansion = 4
+
+    def __init__(self, inplanes, planes, stride=1, downsample=None, BatchNorm=nn.BatchNorm2d):
+        super().__init__()
+        self.conv1 = nn.Conv2d(inplanes, planes, kernel_size=1, bias=False)
+        self.bn1 = BatchNorm(planes)
+        self.conv2 = nn.Conv2d(planes, planes, kernel_size=3, stride=stride, padding=1, bias=False)
+        self.bn2 = BatchNorm(planes)
+        self.conv3 = nn.Conv2d(planes, planes * self.expansion, kernel_size=1, bias=False)
+        self.bn3 = BatchNorm(planes * self.expansion)
+        self.relu = nn.ReLU(inplace=True)
+        self.downsample = downsample
+        self.stride = stride
+
+    def forward(self, x):
+        residual = x
+        out = self.relu(self.bn1(self.conv1(x)))
+        out = self.relu(self.bn2(self.conv2(out)))
+        out = self.bn3(self.conv3(out))
+        if self.downsample is not None:
+            residual = self.downsample(x)
+        out += residual
+        return self.relu(out)
+
+
+def _make_layer(inplanes, planes, blocks, stride, BatchNorm):
+    """resnet_ddcat.py:146-166"""
+    downsample = None
+    if stride != 1 or inplanes != planes * Bottleneck.expansion:
+        downsample = nn.Sequential(nn.Conv2d(inplanes, planes * Bottleneck.expansion, kernel_size=1, stride=stride,
+                                             bias=False), BatchNorm(planes * Bottleneck.expansion))
+    layers = [Bottleneck(inplanes, planes, stride, downsample, BatchNorm)]
+    layers += [Bottleneck(planes * Bottleneck.expansion, planes, BatchNorm=BatchNorm) for _ in range(1, blocks)]
+    return nn.Sequential(*layers)
+
+
+class PPM(nn.Module):
+    """ddcat_psp.py:8-30"""
+
+    def __init__(self, in_dim, reduction_dim, bins, BatchNorm):
+        super().__init__()
+        self.features = nn.ModuleList(
+            nn.Sequential(nn.AdaptiveAvgPool2d(b), nn.Conv2d(in_dim, reduction_dim, kernel_size=1, bias=False),
+                          BatchNorm(reduction_dim), nn.ReLU(inplace=True)) for b in bins)
+
+    def forward(self, x):
+        size = x.shape[2:]
+        return torch.cat([x] + [F.interpolate(f(x), size, mode="bilinear", align_corners=True) for f in self.features], 1)
+
+
+def _conv3x3(cin, cout, stride=1):
+    return nn.Conv2d(cin, cout, kernel_size=3, stride=stride, padding=1, bias=False)
+
+
+class PSPNet(nn.Module):
+    """``PSPNet(50, n_cls)`` of the reference (ddcat_psp.py:372-486).  ``pretrained`` is accepted and ignored (the
+    reference reads fixed cluster paths there); only ``layers=50`` with ``clean=True`` is built."""
+
+    def __init__(self, layers=50, classes=21, bins=(1, 2, 3, 6), dropout=0.1, zoom_factor=8, use_ppm=True,
+                 criterion=nn.CrossEntropyLoss(ignore_index=-1), BatchNorm=nn.BatchNorm2d, pretrained=True, clean=True):
+        super().__init__()
+        if layers != 50:
+            raise ValueError(f"PSPNet: only layers=50 is built here, got {layers}")
+        if not clean:
+            raise ValueError("PSPNet: only the clean=True deep-base ResNet-50 is built here")
+        assert 2048 % len(bins) == 0
+        assert classes > 1
+        assert zoom_factor in [1, 2, 4, 8]
+        self.zoom_factor = zoom_factor
+        self.use_ppm = use_ppm
+        self.criterion = criterion
+        self.layer0 = nn.Sequential(_conv3x3(3, 64, 2), BatchNorm(64), nn.ReLU(inplace=True),
+                                    _conv3x3(64, 64), BatchNorm(64), nn.ReLU(inplace=True),
+                                    _conv3x3(64, 128), BatchNorm(128), nn.ReLU(inplace=True),
+                                    nn.MaxPool2d(kernel_size=3, stride=2, padding=1))
+        self.layer1 = _make_layer(128, 64, 3, 1, BatchNorm)
+        self.layer2 = _make_layer(256, 128, 4, 2, BatchNorm)
+        self.layer3 = _make_layer(512, 256, 6, 2, BatchNorm)
+        self.layer4 = _make_layer(1024, 512, 3, 2, BatchNorm)
+        for m in self.modules():                                        # resnet_ddcat.py:139-144
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+            elif isinstance(m, BatchNorm):
+                nn.init.constant_(m.weight, 1)
+                nn.init.constant_(m.bias, 0)
+        for n, m in self.layer3.named_modules():                        # ddcat_psp.py:429-438
+            if "conv2" in n:
+                m.dilation, m.padding, m.stride = (2, 2), (2, 2), (1, 1)
+            elif "downsample.0" in n:
+                m.stride = (1, 1)
+        for n, m in self.layer4.named_modules():
+            if "conv2" in n:
+                m.dilation, m.padding, m.stride = (4, 4), (4, 4), (1, 1)
+            elif "downsample.0" in n:
+                m.stride = (1, 1)
+        fea_dim = 2048
+        if use_ppm:
+            self.ppm = PPM(fea_dim, int(fea_dim / len(bins)), bins, BatchNorm)
+            fea_dim *= 2
+        self.cls = nn.Sequential(nn.Conv2d(fea_dim, 512, kernel_size=3, padding=1, bias=False), BatchNorm(512),
+                                 nn.ReLU(inplace=True), nn.Dropout2d(p=dropout), nn.Conv2d(512, classes, kernel_size=1))
+        if self.training:        # always true here: the reference's key list has aux.*
+            self.aux = nn.Sequential(nn.Conv2d(1024, 256, kernel_size=3, padding=1, bias=False), BatchNorm(256),
+                                     nn.ReLU(inplace=True), nn.Dropout2d(p=dropout), nn.Conv2d(256, classes, kernel_size=1))
+
+    def _native_ok(self, x, indicate):
+        return (USE_NATIVE and not self.training and indicate != 1 and x.is_cuda and x.dtype == torch.float32
+                and x.dim() == 4 and not torch.is_autocast_enabled() and not any(p.requires_grad for p in self.parameters()))
+
+    def forward(self, x, y=None, indicate=0):
+        x_size = x.size()
+        assert (x_size[2] - 1) % 8 == 0 and (x_size[3] - 1) % 8 == 0
+        h = int((x_size[2] - 1) / 8 * self.zoom_factor + 1)
+        w = int((x_size[3] - 1) / 8 * self.zoom_factor + 1)
+        if self._native_ok(x, indicate):
+            return _native_forward(self, x, (h, w))
+
+        x = self.layer0(x)
+        x = self.layer1(x)
+        x = self.layer2(x)
+        x_tmp = self.layer3(x)
+        x = self.layer4(x_tmp)
+        if self.use_ppm:
+            x = self.ppm(x)
+        x = self.cls(x)
+        if self.zoom_factor != 1:
+            x = F.interpolate(x, size=(h, w), mode="bilinear", align_corners=True)
+        if self.training or indicate == 1:
+            aux = self.aux(x_tmp)
+            if self.zoom_factor != 1:
+                aux = F.interpolate(aux, size=(h, w), mode="bilinear", align_corners=True)
+            main_loss = self.criterion(x, y)
+            aux_loss = self.criterion(aux, y)
+            return main_loss, aux_loss, x
+        return x
+
+
+# ---------------------------------------------------------------------------------------------------- device path
+class _Polyphase(torch.autograd.Function):
+    """P1 split (x -> the d*d sub-images as one batch, or phase (0, 0) alone); backward = merge"""
+
+    @staticmethod
+    @_fp32_fwd
+    def forward(ctx, x, d, first_only):
+        from .. import _native as N
+        ctx.size, ctx.d, ctx.first = tuple(x.shape[2:]), d, first_only
+        return N.polyphase_split(_dense_cl(x), d, first_only)
+
+    @staticmethod
+    @_fp32_bwd
+    def backward(ctx, g):
+        from .. import _native as N
+        return N.polyphase_merge(_dense_cl(g), ctx.size, ctx.d, ctx.first), None, None
+
+
+class _PolyphaseMerge(torch.autograd.Function):
+    """P1 merge (the d*d sub-images -> the full map, tails cropped); backward = split"""
+
+    @staticmethod
+    @_fp32_fwd
+    def forward(ctx, y, size, d):
+        from .. import _native as N
+        ctx.d = d
+        return N.polyphase_merge(_dense_cl(y), size, d)
+
+    @staticmethod
+    @_fp32_bwd
+    def backward(ctx, g):
+        from .. import _native as N
+        return N.polyphase_split(_dense_cl(g), ctx.d), None, None
+
+
+class _AddRelu(torch.autograd.Function):
+    """P3: relu(a + r) of two dense channels_last maps; backward: the output-gated gradient, to both inputs"""
+
+    @staticmethod
+    @_fp32_fwd
+    def forward(ctx, a, r):
+        from .. import _native as N
+        y = N.add_relu(_dense_cl(a), _dense_cl(r))
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    @_fp32_bwd
+    def backward(ctx, g):
+        from .. import _native as N
+        (y,) = ctx.saved_tensors
+        gx = N.add_relu_backward(g if g.stride() == y.stride() else g.contiguous(memory_format=_CL), y)
+        return gx, gx
+
+
+class _UpsampleAC(torch.autograd.Function):
+    """P2: F.interpolate(x, size, mode="bilinear", align_corners=True) of NCHW logits, forward and input gradient"""
+
+    @staticmethod
+    @_fp32_fwd
+    def forward(ctx, x, size):
+        from .. import _native as N
+        ctx.in_size = tuple(x.shape[2:])
+        return N.upsample_ac(x.contiguous(), size)
+
+    @staticmethod
+    @_fp32_bwd
+    def backward(ctx, g):
+        from .. import _native as N
+        return N.upsample_ac_backward(g.contiguous(), ctx.in_size), None
+
+
+class _UpCatAC(torch.autograd.Function):
+    """P2: torch.cat([x] + [up_ac(t) for t in ts], 1) as one channels_last buffer; every up-sampled branch is written
+    straight into its channel slice, and its gradient is gathered straight out of the matching slice"""
+
+    @staticmethod
+    @_fp32_fwd
+    def forward(ctx, size, x, *ts):
+        from .. import _native as N
+        B, Cx, (H, W) = x.shape[0], x.shape[1], size
+        buf = torch.empty(B, Cx + sum(t.shape[1] for t in ts), H, W, dtype=torch.float32, device=x.device, memory_format=_CL)
+        buf[:, :Cx].copy_(x)
+        off = Cx
+        for t in ts:
+            N.upsample_ac_cl(_dense_cl(t), size, out=buf[:, off:off + t.shape[1]])
+            off += t.shape[1]
+        ctx.cx, ctx.shapes = Cx, [tuple(t.shape) for t in ts]
+        return buf
+
+    @staticmethod
+    @_fp32_bwd
+    def backward(ctx, g):
+        from .. import _native as N
+        if N.cl_pixel_stride(g) != g.shape[1]:
+            g = g.contiguous(memory_format=_CL)
+        grads, off = [None, g[:, :ctx.cx]], ctx.cx
+        for shp in ctx.shapes:
+            grads.append(N.upsample_ac_cl_backward(g[:, off:off + shp[1]], shp[2:]))
+            off += shp[1]
+        return tuple(grads)
+
+
+def _cache(mod):
+    if not hasattr(mod, "_psp_cache"):
+        object.__setattr__(mod, "_psp_cache", {})
+    return mod._psp_cache
+
+
+def _pointwise(conv, bn, x, relu):
+    """bn(conv1x1(x)) (+ ReLU) of a dense channels_last map through M8, the eval BatchNorm folded into the weights / bias"""
+    cache = _cache(conv)
+    scale, shift = _folded_bn(bn, conv.bias, cache)
+    key = (_tkey(conv.weight), cache["bn_key"])
+    if cache.get("pw_key") != key:
+        with torch.no_grad():
+            w = conv.weight
+            cache.update(pw_key=key, pw_w=_stable(cache.get("pw_w"), (w.view(w.shape[0], -1) * scale[:, None]).contiguous()))
+    x = _dense_cl(x)
+    B, C, H, W = x.shape
+    x4 = x.permute(0, 2, 3, 1)
+    if relu:
+        x2 = x4.reshape(B * H * W, C)
+        if _split_ok(x2, C):
+            y = _PointwiseRelu.apply(x2, cache["pw_w"], shift, cache, B)
+        else:
+            y = torch.relu_(torch.addmm(shift, x2, cache["pw_w"].t()))
+        return y.view(B, H, W, -1).permute(0, 3, 1, 2)
+    return _linear_frozen(cache, x4, cache["pw_w"], shift).permute(0, 3, 1, 2)
+
+
+def _dilated_ok(conv, x):
+    """the dilated 3x3 convolutions of layer3 / layer4 through P1 + Winograd.  Eligibility by the pixels of ONE image's
+    d*d sub-images together (so an image's arithmetic does not depend on its batch partners)"""
+    d = conv.dilation[0]
+    hs, ws = -(-x.shape[2] // d), -(-x.shape[3] // d)
+    return (d > 1 and conv.dilation == (d, d) and conv.padding == (d, d) and conv.stride == (1, 1)
+            and conv.kernel_size == (3, 3) and conv.groups == 1 and conv.padding_mode == "zeros"
+            and _M.WINOGRAD_TILE in (2, 4) and conv.in_channels % 4 == 0 and conv.out_channels % 4 == 0
+            and d * d * hs * ws >= _M.WINOGRAD_MIN_PIXELS)
+
+
+def dilated_conv3x3(x, weight, d, cache, scale=None, shift=None, relu=False):
+    """act(scale[c] * conv2d(x, weight, padding=d, dilation=d) + shift[c]) for frozen 3x3 filters: P1 split -> the
+    Winograd convolution of the B*d*d sub-images -> P1 merge, forward and input gradient (exact re-indexing: the zero
+    tails of the sub-images are the convolution's zero padding).  ``relu`` needs ``scale`` / ``shift`` (as _WinoConv3x3)."""
+    s = _Polyphase.apply(x, d, False)
+    y = _WinoConv3x3.apply(s, weight, _M.WINOGRAD_TILE, cache, scale, shift, relu)
+    return _PolyphaseMerge.apply(y, tuple(x.shape[2:]), d)
+
+
+def _conv3x3_bn_relu(conv, bn, x):
+    """relu(bn(conv(x))) for a 3x3 convolution of the frozen model"""
+    if conv.stride == (1, 1) and conv.dilation == (1, 1) and _wino_ok(conv, x):
+        scale, shift = _folded_bn(bn, conv.bias, _cache(conv))
+        return _WinoConv3x3.apply(_dense_cl(x), conv.weight, _M.WINOGRAD_TILE, _cache(conv), scale, shift, True)
+    if _dilated_ok(conv, x):
+        scale, shift = _folded_bn(bn, conv.bias, _cache(conv))
+        return dilated_conv3x3(x, conv.weight, conv.dilation[0], _cache(conv), scale, shift, True)
+    return F.relu(bn(conv(x)))                      # library: stem conv1, layer2's strided 3x3, small maps
+
+
+def _block(blk, x):
+    out = _pointwise(blk.conv1, blk.bn1, x, True)
+    out = _conv3x3_bn_relu(blk.conv2, blk.bn2, out)
+    out = _pointwise(blk.conv3, blk.bn3, out, False)
+    if blk.downsample is not None:
+        conv, bn = blk.downsample[0], blk.downsample[1]
+        if conv.stride == (1, 1):
+            residual = _pointwise(conv, bn, x, False)
+        elif conv.stride == (2, 2) and x.shape[1] % 4 == 0:
+            residual = _pointwise(conv, bn, _Polyphase.apply(x, 2, True), False)
+        else:
+            residual = bn(conv(x))
+    else:
+        residual = x
+    return _AddRelu.apply(out, residual)
+
+
+def _native_forward(model, x, size):
+    l0 = model.layer0
+    x = x.contiguous(memory_format=_CL)
+    x = F.relu(l0[1](l0[0](x)))                     # stride 2, 3 input channels: the library (MIOpen)
+    x = _conv3x3_bn_relu(l0[3], l0[4], x)
+    x = _conv3x3_bn_relu(l0[6], l0[7], x)
+    x = _dense_cl(l0[9](x))
+    for layer in (model.layer1, model.layer2, model.layer3, model.layer4):
+        for blk in layer:
+            x = _block(blk, x)
+    if model.use_ppm:
+        branches = [_pointwise(f[1], f[2], _adaptive_pool(f[0], x), True) for f in model.ppm.features]
+        x = _UpCatAC.apply(tuple(x.shape[2:]), x, *branches)
+    y = _conv3x3_bn_relu(model.cls[0], model.cls[1], x)
+    logits = _classify(model.cls[4], _dense_cl(y))
+    if model.zoom_factor == 1:
+        return logits
+    return _UpsampleAC.apply(logits.contiguous(), size)

@@ -187,6 +187,9 @@ def build_model(cfg, random_init: bool, device):
         from semseg.utils.utils import load_config_segmenter
         mcfg, _ = load_config_segmenter(backbone=model_cfg["BACKBONE"], n_cls=test_cfg["N_CLS"])
         model = create_segmenter(mcfg, None, test_cfg["BACKBONE"])
+    elif model_cfg["NAME"] == "PSPNet":
+        from semseg.models import PSPNet
+        model = PSPNet(50, test_cfg["N_CLS"])            # the reference's eval(MODEL.NAME)(50, N_CLS) (tools/infer.py:266-268)
     else:
         raise ValueError(f"model family {model_cfg['NAME']} is outside this build (SURVEY 2.1)")
     if not random_init:
