@@ -612,6 +612,31 @@ int sea_psp_upsample_ac_nhwc_bwd(const float* gy, float* gx, float* work, int B,
 int sea_psp_add_relu(const float* a, const float* r, float* y, int64_t n, void* stream);
 int sea_psp_add_relu_bwd(const float* gy, const float* y, float* gx, int64_t n, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * T1: train-mode BatchNorm2d of PSPNet-ResNet50's PIR-AT outer step (the reference trains every nn.BatchNorm2d of
+ * backbones/resnet_ddcat.py and ddcat_psp.py on batch statistics: tools/train_rob_seg.py:338-340), fused with the ReLU or
+ * residual-add + ReLU that follows it (resnet_ddcat.py:97-105; ddcat_psp.py:21, 441-446).  fp32, x dense NHWC = an
+ * (M, C) row-major matrix, M = B*H*W >= 2 rows, C % 4 == 0, every pointer 16-byte aligned.  No float atomics: the
+ * results are bitwise reproducible.
+ * sea_bn_train_workspace_floats: the floats of `work` that both calls below need for (M, C); -1 if unsupported.
+ * sea_bn_train_fwd: torch.nn.functional.batch_norm(x, running_mean, running_var, gamma, beta, training=True, momentum,
+ *   eps): mean and biased variance over the M rows (fixed-order two-stage Welford / Chan reduction), invstd =
+ *   1/sqrt(var + eps), scale = gamma*invstd (all three written, C floats each), then y = (x - mean)*scale + beta
+ *   [+ r] [ReLU] (r: NULL or an (M, C) residual; relu: 0 / 1).  running_mean <- (1-momentum)*
+ *   running_mean + momentum*mean, running_var <- (1-momentum)*running_var + momentum*var*M/(M-1) and
+ *   *num_batches_tracked += 1, as torch's _BatchNorm does with a float momentum; each of the three may be NULL (no update).
+ * sea_bn_train_bwd: the gradient of sea_bn_train_fwd from dL/dy g: g' = relu ? (y > 0 ? g : 0) : g (y: the saved
+ *   output), dbeta = sum g', dgamma = sum g'*xhat with xhat = (x - mean)*invstd, dx = scale*(g' - dbeta/M -
+ *   xhat*dgamma/M), as torch's batch_norm_backward with training=True.  gr (the residual variant, relu = 1 only): g', the
+ *   gradient of r; NULL otherwise.  mean / invstd / scale: the forward's outputs. */
+int64_t sea_bn_train_workspace_floats(int64_t M, int C);
+int sea_bn_train_fwd(const float* x, const float* r, const float* gamma, const float* beta, float* y, float* mean,
+                     float* invstd, float* scale, float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                     float* work, int64_t M, int C, float eps, float momentum, int relu, void* stream);
+int sea_bn_train_bwd(const float* g, const float* x, const float* y, const float* mean, const float* invstd,
+                     const float* scale, float* dx, float* dgamma, float* dbeta, float* gr, float* work, int64_t M, int C,
+                     int relu, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,7 @@ SOURCES = [
     ("classifier.hip", []),
     ("msf_kernels.hip", ["-ffp-contract=off"]),
     ("psp_kernels.hip", []),
+    ("bn_train.hip", []),
     ("greedy_host.cpp", ["-ffp-contract=off"]),
     ("api_misc.cpp", []),
 ]

@@ -122,6 +122,9 @@ _SIGS = {
     "sea_psp_upsample_ac_nhwc_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "sea_psp_add_relu": (_i, [_vp, _vp, _vp, _i64, _vp]),
     "sea_psp_add_relu_bwd": (_i, [_vp, _vp, _vp, _i64, _vp]),
+    "sea_bn_train_workspace_floats": (_i64, [_i64, _i]),
+    "sea_bn_train_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _f, _f, _i, _vp]),
+    "sea_bn_train_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _vp]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -531,6 +534,73 @@ def add_relu_backward(gy, y):
     gx = torch.empty_like(y)
     _check(lib().sea_psp_add_relu_bwd(_p(gy), _p(y), _p(gx), y.numel(), _stream()), "sea_psp_add_relu_bwd")
     return gx
+
+
+# ------------------------------------------------------------------------------------------------ T1 (PSPNet training)
+def _bn_rows(t, what):
+    """(M, C) of a dense channels_last float32 (B, C, H, W) tensor (a 1 x 1 map included)"""
+    if t.dim() != 4 or t.dtype != torch.float32 or t.shape[1] % 4 or not _nhwc_dense(t) or t.data_ptr() % 16:
+        raise SeaNativeError(f"{what}: dense channels_last float32 (B,C,H,W) with C % 4 == 0 expected")
+    B, Cc, H, W = t.shape
+    return B * H * W, Cc
+
+
+def _bn_work(M, Cc, device):
+    n = lib().sea_bn_train_workspace_floats(M, Cc)
+    if n < 0:
+        raise SeaNativeError(f"bn_train: unsupported shape M={M}, C={Cc}")
+    return torch.empty(n, dtype=torch.float32, device=device)
+
+
+def bn_train_forward(x, weight, bias, running_mean=None, running_var=None, num_batches_tracked=None, eps: float = 1e-5,
+                     momentum: float = 0.1, relu: bool = False, residual=None):
+    """T1: F.batch_norm(x, running_mean, running_var, weight, bias, training=True, momentum, eps) of a dense channels_last
+    fp32 map, then ``+ residual`` and / or ReLU.  Returns (y, mean, invstd, scale) (y channels_last like x; the three
+    per-channel vectors are what ``bn_train_backward`` needs).  The running buffers are updated in place by the kernel and
+    their version counters advanced, as a torch in-place op would (caches keyed on ``_version`` see the change)."""
+    _dev(x, weight, bias, running_mean, running_var, num_batches_tracked, residual)
+    M, Cc = _bn_rows(x, "bn_train_forward")
+    if M < 2:
+        raise SeaNativeError("bn_train_forward: batch statistics need more than one value per channel")
+    for t in (weight, bias, running_mean, running_var):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != Cc):
+            raise SeaNativeError("bn_train_forward: per-channel float32 vectors of length C expected")
+    if num_batches_tracked is not None and (num_batches_tracked.dtype != torch.int64 or num_batches_tracked.numel() != 1):
+        raise SeaNativeError("bn_train_forward: num_batches_tracked must be one int64")
+    if residual is not None and (residual.shape != x.shape or _bn_rows(residual, "bn_train_forward") != (M, Cc)):
+        raise SeaNativeError("bn_train_forward: residual must match x's shape")
+    y = torch.empty_like(x)
+    vec = torch.empty(3, Cc, dtype=torch.float32, device=x.device)
+    mean, invstd, scale = vec[0], vec[1], vec[2]
+    _check(lib().sea_bn_train_fwd(_p(x), _p(residual), _p(weight), _p(bias), _p(y), _p(mean), _p(invstd), _p(scale),
+                                  _p(running_mean), _p(running_var), _p(num_batches_tracked),
+                                  _p(_bn_work(M, Cc, x.device)), M, Cc, float(eps), float(momentum), int(bool(relu)),
+                                  _stream()), "sea_bn_train_fwd")
+    for t in (running_mean, running_var, num_batches_tracked):
+        if t is not None:
+            torch.autograd.graph.increment_version(t)
+    return y, mean, invstd, scale
+
+
+def bn_train_backward(gy, x, y, mean, invstd, scale, relu: bool = False, residual_grad: bool = False):
+    """T1 backward: (dx, dweight, dbias, dresidual or None) of ``bn_train_forward`` from dL/dy ``gy`` (same layout as x);
+    ``y`` the forward's output (read for the ReLU gate, may be None without ``relu``)."""
+    _dev(gy, x, y, mean, invstd, scale)
+    M, Cc = _bn_rows(x, "bn_train_backward")
+    if gy.shape != x.shape or (relu and (y is None or y.shape != x.shape)):
+        raise SeaNativeError("bn_train_backward: gy (and y) must match x's shape")
+    _bn_rows(gy, "bn_train_backward")
+    if relu:
+        _bn_rows(y, "bn_train_backward")
+    if residual_grad and not relu:
+        raise SeaNativeError("bn_train_backward: the residual variant is relu(x*scale + shift + r)")
+    dx = torch.empty_like(x)
+    gr = torch.empty_like(x) if residual_grad else None
+    dvec = torch.empty(2, Cc, dtype=torch.float32, device=x.device)
+    _check(lib().sea_bn_train_bwd(_p(gy), _p(x), _p(y if relu else None), _p(mean), _p(invstd), _p(scale), _p(dx),
+                                  _p(dvec[0]), _p(dvec[1]), _p(gr), _p(_bn_work(M, Cc, x.device)), M, Cc, int(bool(relu)),
+                                  _stream()), "sea_bn_train_bwd")
+    return dx, dvec[0], dvec[1], gr
 
 
 def count_ignored(y, out=None):

@@ -3,8 +3,8 @@ backbones/resnet_ddcat.py:110-131): the VOC model of the reference's tools/infer
 configs/voc_pspnet_cais.yaml) and the architecture of the DDC-AT / CAIS baselines.
 
 Same modules, names and state-dict keys as the reference (370 keys, ``aux.*`` included), so a reference checkpoint loads
-with ``strict=True``.  Training mode (and ``indicate == 1``) runs the reference's forward on plain torch ops.  The frozen
-eval forward of a float32 device batch -- what SEA attacks -- and its input gradient run on the device kernels
+with ``strict=True``.  ``indicate == 1``, bf16 autocast and CPU tensors run the reference's forward on plain torch ops.  The
+frozen eval forward of a float32 device batch -- what SEA attacks -- and its input gradient run on the device kernels
 ("PSPNet"):
 
 - 1x1 convolutions (stride 1): M8 with the eval BatchNorm folded in (``_PointwiseRelu`` / ``_linear_frozen``);
@@ -17,7 +17,12 @@ eval forward of a float32 device batch -- what SEA attacks -- and its input grad
 The stem's stride-2 3-input-channel convolution, layer2's stride-2 3x3 and the max-pool stay with the library (about 1 %
 of the FLOPs).  There is deliberately no ``forward_lowres`` hook: K2u and K10b assume align_corners=False.
 
-``USE_NATIVE = False`` runs the plain torch forward in eval mode too (A/B runs, the stock yardstick of the tests)."""
+Training mode (PIR-AT's outer step, tools/train_rob_seg.py) of a float32 device batch keeps the reference's module order and
+return value ``(main_loss, aux_loss, x)``; every BatchNorm runs on T1 (train-mode statistics, running-buffer update and
+the following ReLU / residual add + ReLU in HIP) after the library convolution, the dilated 3x3 convolutions become P1
+split -> dense 3x3 convolutions of the B*d*d sub-images -> P1 merge, and the align_corners=True up-samplings run on P2.
+
+``USE_NATIVE = False`` runs the plain torch forward in both modes (A/B runs, the stock yardstick of the tests)."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -142,6 +147,10 @@ class PSPNet(nn.Module):
         return (USE_NATIVE and not self.training and indicate != 1 and x.is_cuda and x.dtype == torch.float32
                 and x.dim() == 4 and not torch.is_autocast_enabled() and not any(p.requires_grad for p in self.parameters()))
 
+    def _native_train_ok(self, x, indicate):
+        return (USE_NATIVE and self.training and indicate != 1 and x.is_cuda and x.dtype == torch.float32
+                and x.dim() == 4 and not torch.is_autocast_enabled())
+
     def forward(self, x, y=None, indicate=0):
         x_size = x.size()
         assert (x_size[2] - 1) % 8 == 0 and (x_size[3] - 1) % 8 == 0
@@ -149,6 +158,8 @@ class PSPNet(nn.Module):
         w = int((x_size[3] - 1) / 8 * self.zoom_factor + 1)
         if self._native_ok(x, indicate):
             return _native_forward(self, x, (h, w))
+        if self._native_train_ok(x, indicate):
+            return _native_train_forward(self, x, y, (h, w))
 
         x = self.layer0(x)
         x = self.layer1(x)
@@ -367,3 +378,109 @@ def _native_forward(model, x, size):
     if model.zoom_factor == 1:
         return logits
     return _UpsampleAC.apply(logits.contiguous(), size)
+
+
+# ---------------------------------------------------------------------------------------------------- training path
+class _BNTrain(torch.autograd.Function):
+    """T1: [relu](batch_norm(x, training=True) [+ r]) of a dense channels_last map.  gamma / beta are inputs (their
+    gradients reach DDP's hooks); the running buffers of ``bn`` are updated in place."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, r, bn, relu):
+        from .. import _native as N
+        x = _nhwc(x)
+        y, mean, invstd, scale = N.bn_train_forward(x, weight, bias, bn.running_mean, bn.running_var,
+                                                    bn.num_batches_tracked, bn.eps, bn.momentum, relu,
+                                                    None if r is None else _nhwc(r))
+        ctx.relu, ctx.res = relu, r is not None
+        ctx.save_for_backward(x, y if relu else None, mean, invstd, scale)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        from .. import _native as N
+        x, y, mean, invstd, scale = ctx.saved_tensors
+        dx, dw, db, gr = N.bn_train_backward(_nhwc(g), x, y, mean, invstd, scale, ctx.relu, ctx.res)
+        return dx, dw, db, gr, None, None
+
+
+def _nhwc(t):
+    """``t`` itself if its memory is dense NHWC (a 1 x 1 map in either stride form included), else a channels_last copy"""
+    return t if t.is_contiguous(memory_format=_CL) else t.contiguous(memory_format=_CL)
+
+
+def _t1_ok(bn, x):
+    """what T1 covers: an affine BatchNorm2d on batch statistics with a float momentum, fp32 device maps, C % 4 == 0"""
+    return (type(bn) is nn.BatchNorm2d and bn.training and bn.affine and bn.track_running_stats
+            and bn.momentum is not None and bn.weight.dtype == torch.float32 and x.dtype == torch.float32 and x.is_cuda
+            and x.dim() == 4 and x.shape[1] % 4 == 0 and x.shape[0] * x.shape[2] * x.shape[3] >= 2)
+
+
+def _bn_train(bn, x, relu, r=None):
+    """[relu](bn(x) [+ r]) in training mode: T1, or the torch modules where T1 does not apply"""
+    if _t1_ok(bn, x):
+        return _BNTrain.apply(x, bn.weight, bn.bias, r, bn, relu)
+    y = bn(x)
+    if r is not None:
+        y = y + r
+    return F.relu(y) if relu else y
+
+
+def _dilated_train_ok(conv, x):
+    d = conv.dilation[0]
+    return (d > 1 and conv.dilation == (d, d) and conv.padding == (d, d) and conv.stride == (1, 1)
+            and conv.kernel_size == (3, 3) and conv.groups == 1 and conv.padding_mode == "zeros" and conv.bias is None
+            and x.is_cuda and x.dtype == torch.float32 and x.shape[1] % 4 == 0)
+
+
+def dilated_conv3x3_train(x, weight, d):
+    """conv2d(x, weight, padding=d, dilation=d) of a trainable 3x3 filter: P1 split -> the library's dense 3x3 / pad-1
+    convolution of the B*d*d sub-images -> P1 merge.  The exact re-indexing of ``dilated_conv3x3``: the weight and input
+    gradients flow through autograd, and the library only sees dense 3x3 convolutions."""
+    s = _Polyphase.apply(x, d, False)
+    return _PolyphaseMerge.apply(F.conv2d(s, weight, padding=1), tuple(x.shape[2:]), d)
+
+
+def _conv_train(conv, x):
+    if _dilated_train_ok(conv, x):
+        return dilated_conv3x3_train(x, conv.weight, conv.dilation[0])
+    return conv(x)
+
+
+def _block_train(blk, x):
+    out = _bn_train(blk.bn1, blk.conv1(x), True)
+    out = _bn_train(blk.bn2, _conv_train(blk.conv2, out), True)
+    out = blk.conv3(out)
+    residual = x if blk.downsample is None else _bn_train(blk.downsample[1], blk.downsample[0](x), False)
+    return _bn_train(blk.bn3, out, True, residual)
+
+
+def _up_ac_train(t, size):
+    return _UpsampleAC.apply(t.contiguous(), size)
+
+
+def _native_train_forward(model, x, y, size):
+    """``PSPNet.forward`` in training mode (ddcat_psp.py:453-478) on the device path: same modules in the same order"""
+    l0 = model.layer0
+    x = x.contiguous(memory_format=_CL)
+    x = _bn_train(l0[1], l0[0](x), True)
+    x = _bn_train(l0[4], _conv_train(l0[3], x), True)
+    x = _bn_train(l0[7], _conv_train(l0[6], x), True)
+    x = l0[9](x)
+    for layer in (model.layer1, model.layer2, model.layer3):
+        for blk in layer:
+            x = _block_train(blk, x)
+    x_tmp = x
+    for blk in model.layer4:
+        x = _block_train(blk, x)
+    if model.use_ppm:
+        branches = [_bn_train(f[2], f[1](f[0](x)), True) for f in model.ppm.features]
+        x = _UpCatAC.apply(tuple(x.shape[2:]), _dense_cl(x), *[_dense_cl(b) for b in branches])
+    cls, aux = model.cls, model.aux
+    x = cls[4](cls[3](_bn_train(cls[1], _conv_train(cls[0], x), True)))
+    if model.zoom_factor != 1:
+        x = _up_ac_train(x, size)
+    a = aux[4](aux[3](_bn_train(aux[1], _conv_train(aux[0], x_tmp), True)))
+    if model.zoom_factor != 1:
+        a = _up_ac_train(a, size)
+    return model.criterion(x, y), model.criterion(a, y), x

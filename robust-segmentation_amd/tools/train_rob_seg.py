@@ -17,7 +17,10 @@ adversarial batch + optimizer + LR schedule].  What differs from the reference:
     the inner steps; the attack kernels take bf16 logits natively;
   * data: synthetic (datasets are out of scope).
 Optimizer param groups and the warm-up + polynomial LR schedule follow semseg/optimizers.py:13-59 and
-semseg/schedulers.py:80-134.
+semseg/schedulers.py:80-134.  PSPNet (configs/pascalvoc_pspnet.yaml) follows the reference's own recipe instead
+(tools/train_rob_seg.py:92-98, 185-204, 338-361): ``PSPNet(50, N_CLS)``, loss = main_loss + 0.4 * aux_loss, SGD over eight
+parameter groups (layer0-4, then ppm, cls, aux) and the poly rule set after every step, x10 on the new modules, with no
+warm-up (SCHEDULER is ignored).  Its crops satisfy (H - 1) % 8 == 0.
 """
 from __future__ import annotations
 
@@ -37,7 +40,7 @@ if _PKG not in sys.path:
     sys.path.insert(0, _PKG)
 
 from semseg import attacker  # noqa: E402
-from semseg.models import UperNetForSemanticSegmentation, create_segmenter  # noqa: E402
+from semseg.models import PSPNet, UperNetForSemanticSegmentation, create_segmenter  # noqa: E402
 from semseg.val import Pgd_Attack, Pgd_Attack_1  # noqa: E402
 
 
@@ -67,6 +70,27 @@ def warmup_poly_lambda(power, max_iter, warmup_iter, warmup_ratio, warmup="exp")
         a = (it - warmup_iter) / max(max_iter - warmup_iter, 1)
         return max(1 - a, 0.0) ** power
     return ratio
+
+
+def psp_param_groups(model, lr):
+    """the reference's PSPNet parameter groups (train_rob_seg.py:185-200): layer0 .. layer4, then ppm, cls, aux"""
+    mods = [model.layer0, model.layer1, model.layer2, model.layer3, model.layer4, model.ppm, model.cls, model.aux]
+    return [dict(params=list(m.parameters()), lr=lr) for m in mods]
+
+
+PSP_NEW_GROUPS = 5  # groups 5.. (ppm, cls, aux) run at 10x the backbone's rate
+
+
+def poly_lr(base_lr, it, max_iter, power=0.9):
+    """poly_learning_rate of the reference (train_rob_seg.py:38-41)"""
+    return base_lr * (1 - float(it) / max_iter) ** power
+
+
+def set_psp_lr(opt, base_lr, it, max_iter):
+    """after step ``it``: every backbone group at poly_lr(it), the new modules at 10x (train_rob_seg.py:356-361)"""
+    lr = poly_lr(base_lr, it, max_iter)
+    for k, g in enumerate(opt.param_groups):
+        g["lr"] = lr if k < PSP_NEW_GROUPS else lr * 10
 
 
 def build_attack(train_cfg):
@@ -132,8 +156,11 @@ def _main(argv=None):
         from semseg.utils.utils import load_config_segmenter
         mcfg, _ = load_config_segmenter(backbone=model_cfg["BACKBONE"], n_cls=C)
         model = create_segmenter(mcfg, None, model_cfg["BACKBONE"])
+    elif model_cfg["NAME"] == "PSPNet":
+        model = PSPNet(50, C)
     else:
         raise ValueError(model_cfg["NAME"])
+    psp = model_cfg["NAME"] == "PSPNet"
     model = model.to(dev)
     ddp = DDP(model, device_ids=[dev.index]) if world > 1 else model
     core = model  # the attack always runs on the un-wrapped module: no collective inside the inner loop
@@ -141,22 +168,30 @@ def _main(argv=None):
     virt = max(args.emulate_ranks, 1)  # data-parallel ranks this process stands in for
     bs = args.batch_size or int(train_cfg["BATCH_SIZE"]) // max(world * virt, 1)
     size = int(train_cfg["IMAGE_SIZE"][0])
-    size -= size % 32  # synthetic crops: multiples of 32 keep every feature map integral
+    # synthetic crops: multiples of 32 keep every feature map integral; PSPNet needs (H - 1) % 8 == 0 instead
+    size -= (size - 1) % 8 if psp else size % 32
     n = max(args.synthetic, bs)
 
     def rank_data(r):
         g = torch.Generator().manual_seed(1234 + r)
         im = torch.rand(n, 3, size, size, generator=g)
-        lb = torch.randint(0, C, (n, size // 32, size // 32), generator=g).repeat_interleave(32, 1).repeat_interleave(32, 2)
-        return im, lb
+        k = -(-size // 32)
+        lb = torch.randint(0, C, (n, k, k), generator=g).repeat_interleave(32, 1).repeat_interleave(32, 2)
+        return im, lb[:, :size, :size]
 
     data = [rank_data(rank * virt + v) for v in range(virt)]
 
-    opt = get_optimizer(ddp, cfg["OPTIMIZER"]["NAME"], cfg["OPTIMIZER"]["LR"], cfg["OPTIMIZER"]["WEIGHT_DECAY"])
     total = args.steps + args.warmup
-    sched = torch.optim.lr_scheduler.LambdaLR(opt, warmup_poly_lambda(
-        cfg["SCHEDULER"]["POWER"], max(total, 2), min(int(cfg["SCHEDULER"]["WARMUP"]), total // 2),
-        cfg["SCHEDULER"]["WARMUP_RATIO"]))
+    base_lr = cfg["OPTIMIZER"]["LR"]
+    if psp:
+        opt = torch.optim.SGD(psp_param_groups(core, base_lr), base_lr, momentum=0.9,
+                              weight_decay=cfg["OPTIMIZER"]["WEIGHT_DECAY"])
+        sched = None
+    else:
+        opt = get_optimizer(ddp, cfg["OPTIMIZER"]["NAME"], base_lr, cfg["OPTIMIZER"]["WEIGHT_DECAY"])
+        sched = torch.optim.lr_scheduler.LambdaLR(opt, warmup_poly_lambda(
+            cfg["SCHEDULER"]["POWER"], max(total, 2), min(int(cfg["SCHEDULER"]["WARMUP"]), total // 2),
+            cfg["SCHEDULER"]["WARMUP_RATIO"]))
     amp = bool(train_cfg["AMP"]) or args.bf16
     attack_fn = build_attack(train_cfg) if train_cfg["ADVERSARIAL"] else None
 
@@ -182,7 +217,10 @@ def _main(argv=None):
                     core.eval()
                     img = attack_fn(core, img, lbl)
                     core.train()
-                if model_cfg["NAME"] == "UperNetForSemanticSegmentation":
+                if psp:
+                    main_loss, aux_loss, _ = ddp(img, lbl)
+                    loss = main_loss + 0.4 * aux_loss
+                elif model_cfg["NAME"] == "UperNetForSemanticSegmentation":
                     loss, _ = ddp(img, lbl)
                 else:
                     loss = torch.nn.functional.cross_entropy(ddp(img), lbl, ignore_index=-1)
@@ -194,7 +232,10 @@ def _main(argv=None):
             for b, b0 in zip(core.buffers(), buf_r0):
                 b.copy_(b0)
         opt.step()
-        sched.step()
+        if psp:
+            set_psp_lr(opt, base_lr, i, total)
+        else:
+            sched.step()
         return first
 
     for i in range(args.warmup):
