@@ -307,27 +307,30 @@ def _capture_stream(device):
 
 
 
-# ---- one captured graph pair for every run of an evaluation ----------------------------------------------------------------
+# ---- one owner for a run's device buffers and its captured graph pair -------------------------------------------------------
 # SEA runs nine apgd_train calls per batch (three losses x three stages, reference attacker.py:691-728 and
 # tools/infer.py:338-370).  Nothing distinguishes them for the captured graphs except the radius, the run length (with its
 # checkpoint table) and the contents of the buffers: all of that is DEVICE STATE here (sea_apgd_linf_step_graph_dev /
-# sea_apgd_track_graph_dev read eps and n_iter from memory), the loss is chosen by the eager K2 launch between the two
-# graphs, and the buffers whose addresses the graphs bake in live in a slot that outlives the run.  The pair is therefore
-# captured ONCE per (model weights, batch shape, classes) and replayed by every stage, loss and batch of equal shape; round
-# 4 captured nine pairs per batch (3.7 % of the protocol's wall time).  SEA_GRAPH_CACHE=0 restores a pair per run.
+# sea_apgd_track_graph_dev read eps and n_iter from memory) and the loss is chosen by the eager K2 launch between the two
+# graphs.  So every run works in the buffers of exactly ONE owner (`_RunBuffers`), which also holds the pair that addresses
+# them: the caller's tensors are copied in and never written, the results are copied out.  An owner cached on the model
+# (`_graph_slot`) outlives its run: the pair is captured ONCE per (model weights, batch shape, classes, K2 or K2u) and replayed
+# by every stage, loss and batch of equal shape; round 4 captured nine pairs per batch (3.7 % of the protocol's wall time).
+# A run that gets no cached owner (eager loop, SEA_GRAPH_CACHE=0, a nested run, weights that moved between two runs, L2)
+# constructs a private one sized for its own length, starts without a pair and frees pair and activation pool on release.
 GRAPH_CACHE = os.environ.get("SEA_GRAPH_CACHE", "1") != "0"
-GRAPH_SLOT_MIN_ITERS = 128      # capacity (iterations) of a slot's checkpoint table and loss history
-_GRAPH_SLOTS = weakref.WeakKeyDictionary()   # model -> {shape key: _GraphSlot}; dies with the model
+GRAPH_SLOT_MIN_ITERS = 128      # capacity (iterations) of a cached owner's checkpoint table and loss history
+_GRAPH_SLOTS = weakref.WeakKeyDictionary()   # model -> {shape key: _RunBuffers}; dies with the model
 
 
-class _GraphSlot:
-    """Buffers with a fixed address for the lifetime of a captured graph pair, the pair itself, and the run-specific
-    scalars as device words."""
+class _RunBuffers:
+    """Every device buffer of one APGD run, at a fixed address for the lifetime of a captured graph pair, the pair itself,
+    and the run-specific scalars (radius, run length, checkpoint table, loop index) as device words."""
 
-    def __init__(self, x, num_classes, cap_iter, weights_key):
+    def __init__(self, x, num_classes, cap_iter, weights_key=None):
         dev, B = x.device, x.shape[0]
         self.weights_key, self.cap_iter = weights_key, cap_iter
-        new = lambda: torch.empty_like(x)  # noqa: E731
+        new = lambda: torch.empty_like(x, memory_format=torch.contiguous_format)  # noqa: E731
         self.x, self.bufs, self.grad = new(), [new(), new(), new()], new()
         self.x_best, self.x_best_adv, self.grad_best = new(), new(), new()
         pred_dtype = torch.uint8 if num_classes <= 255 else torch.int16
@@ -336,17 +339,18 @@ class _GraphSlot:
         self.stats = (torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.float32, device=dev),
                       torch.empty(B, dtype=torch.int32, device=dev))
         self.ws = N.loss_workspace(B, x.shape[-2] * x.shape[-1], dev)
+        self.ws_low = None          # K2u's workspace (sized by the low-resolution logits of the first fused launch)
         self.n_ignored = torch.empty(B, dtype=torch.int32, device=dev)
         self.st = ApgdState(B, cap_iter, 0.0, dev)
         self.it_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         self.cp_dev = torch.zeros(cap_iter, dtype=torch.int32, device=dev)
         self.eps_dev = torch.zeros(1, dtype=torch.float32, device=dev)
         self.niter_dev = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.dlogits = None
+        self.dlogits = None         # K2's / K2u's gradient buffer (allocated by the first launch, see keep_k2_grad)
         self.graphs = None          # (graph A, graph B) once captured
-        self.sig = None             # what else the captured pair bakes in (early_stop, deferred K2 sums)
+        self.sig = None             # what else the captured pair bakes in (early_stop, deferred K2 sums, arithmetic)
         self.g_xin = self.g_logits = self.ws_pin = None
-        self.busy = False           # a run is using the slot (runs are sequential; a nested one gets its own buffers)
+        self.busy = False           # a run is using the owner (runs are sequential; a nested one gets a private owner)
 
     def reset(self, eps, n_iter, cps):
         """the state of a fresh run (reference attacker.py:310-339), written in place"""
@@ -362,7 +366,25 @@ class _GraphSlot:
         self.eps_dev.fill_(eps)
         self.niter_dev.fill_(max(n_iter, 1))
 
+    def k2u_workspace(self, low):
+        if self.ws_low is None:
+            self.ws_low = torch.empty(N.lib().sea_loss_upsampled_workspace_bytes(
+                low.shape[0], low.shape[1], low.shape[2], low.shape[3], self.x.shape[-2], self.x.shape[-1]),
+                dtype=torch.uint8, device=low.device)
+        return self.ws_low
+
+    def keep_k2_grad(self, dlogits):
+        """the kernel wrapper allocates the gradient buffer on the first launch (in the logits' memory format); every later
+        launch of this owner writes the same one, and graph B reads it"""
+        self.dlogits = dlogits
+
+    def keep_graphs(self, graphs, sig, g_xin, g_logits):
+        self.graphs, self.sig, self.g_xin, self.g_logits = graphs, sig, g_xin, g_logits
+        # the graphs bake in the address of the split-K workspace the model's GEMMs used: keep it alive while they may replay
+        self.ws_pin = N.ksplit_workspace_pin(self.x.device)
+
     def drop_graphs(self):
+        """the pair and the activations its private pool keeps alive (several GB at B=8, 512x512)"""
         self.graphs = self.sig = None
         self.g_xin = self.g_logits = self.ws_pin = None
 
@@ -374,17 +396,18 @@ def _weights_key(model):
 
 def _arith_signature(model):
     """Everything process-global that a captured forward / backward bakes in besides addresses and weights: the arithmetic
-    switches of the model modules (every UPPER-CASE scalar global of semseg.models.*: GEMM_TERMS, GEMM_TERMS_BWD,
-    WINOGRAD_TILE, WINOGRAD_MIN_PIXELS, USE_*, FUSE_MLP ...; the in-process override of the GEMM terms), the attention
-    arithmetic (read per call from the environment), the library's K-loop pipeline and MFMA shape, the autocast state and
-    ``model.training``.  A cached pair whose signature differs is captured again instead of replaying the old arithmetic."""
+    and kernel switches of the model modules and of the kernel bindings (every UPPER-CASE scalar global of semseg.models.* and
+    semseg._native: GEMM_TERMS, GEMM_TERMS_BWD, WINOGRAD_TILE, WINOGRAD_MIN_PIXELS, USE_*, FUSE_MLP, WINO_SPLIT_MIN_TILES ...;
+    the in-process override of the GEMM terms), the attention arithmetic (read per call from the environment), the library's
+    K-loop pipeline and MFMA shape, the autocast state and ``model.training``.  A cached pair whose signature differs is
+    captured again instead of replaying the old arithmetic."""
     import sys
     sig = [bool(getattr(model, "training", False)), torch.is_autocast_enabled(),
            str(torch.get_autocast_dtype("cuda")) if torch.is_autocast_enabled() else None,
            N.attn_terms_fwd(), N.attn_terms_bwd(), int(N.lib().sea_gemm_split_pipeline(-1)),
-           int(N.lib().sea_gemm_split_mfma_shape(0)), bool(N.AMAX_FROM_PRODUCERS)]
+           int(N.lib().sea_gemm_split_mfma_shape(0))]
     for name in sorted(sys.modules):
-        if name.startswith("semseg.models."):
+        if name.startswith("semseg.models.") or name == N.__name__:
             mod = sys.modules[name]
             sig.append((name, tuple((k, v) for k, v in sorted(vars(mod).items())
                                     if k.isupper() and isinstance(v, (bool, int, float, str)))))
@@ -396,8 +419,8 @@ def _arith_signature(model):
 class _Volatile:
     """Marker in a model's slot table: the weights behind this shape changed between two runs (a training loop such as
     tools/train_rob_seg.py with ATTACK=apgd, whose every outer step moves the parameters' versions).  Such a run gets NO
-    slot -- it captures its own pair and frees it with its activation pool on return, as before round 5 -- and a slot is
-    attached again only once two consecutive runs saw the same weights."""
+    cached owner -- it captures its own pair and frees it with its activation pool on return, as before round 5 -- and one
+    is attached again only once two consecutive runs saw the same weights."""
 
     def __init__(self, weights_key):
         self.weights_key = weights_key
@@ -406,59 +429,73 @@ class _Volatile:
 GRAPH_SLOTS_PER_MODEL = 2       # shapes kept per model (an evaluation has at most a full and a ragged last batch)
 
 
-def _graph_slot(model, x, num_classes, n_iter):
+def _graph_slot(model, x, num_classes, n_iter, fused):
+    """the model's cached owner for this shape and loss kernel, or None: the run then constructs a private one"""
     if not (GRAPH_CACHE and isinstance(model, torch.nn.Module)):
         return None
     try:
         slots = _GRAPH_SLOTS.setdefault(model, {})
     except TypeError:
         return None
-    key = (tuple(x.shape), x.dtype, x.device.index, num_classes)
+    # `fused`: K2u's gradient buffer is low-resolution, K2's is not, and the pair replays one of the two forwards
+    key = (tuple(x.shape), x.dtype, x.device.index, num_classes, fused)
     wkey = _weights_key(model)
-    slot = slots.pop(key, None)             # (re-inserted below: the dict keeps the most recently used shape last)
-    if isinstance(slot, _Volatile):
-        if slot.weights_key != wkey:        # still moving: no slot, no several GB parked on the model
-            slot.weights_key = wkey
-            slots[key] = slot
+    own = slots.pop(key, None)              # (re-inserted below: the dict keeps the most recently used shape last)
+    if isinstance(own, _Volatile):
+        if own.weights_key != wkey:         # still moving: no cached owner, no several GB parked on the model
+            own.weights_key = wkey
+            slots[key] = own
             return None
-        slot = None                         # the weights held still for two runs: cache again
-    elif slot is not None and slot.weights_key != wkey:
+        own = None                          # the weights held still for two runs: cache again
+    elif own is not None and own.weights_key != wkey:
         # other weights (a training step, a loaded checkpoint): free the stale pair and its pool BEFORE anything new is
         # allocated, and let this run capture for itself
-        slot.drop_graphs()
+        own.drop_graphs()
         slots[key] = _Volatile(wkey)
         return None
-    elif slot is not None and slot.busy:
-        slots[key] = slot
+    elif own is not None and own.busy:
+        slots[key] = own
         return None                         # a nested run gets its own buffers
-    elif slot is not None and slot.cap_iter < n_iter:
-        slot.drop_graphs()                  # a longer run than the tables were sized for: start over
-        slot = None
-    if slot is None:
-        live = [k for k, v in slots.items() if isinstance(v, _GraphSlot)]
+    elif own is not None and own.cap_iter < n_iter:
+        own.drop_graphs()                   # a longer run than the tables were sized for: start over
+        own = None
+    if own is None:
+        live = [k for k, v in slots.items() if isinstance(v, _RunBuffers)]
         while len(live) >= GRAPH_SLOTS_PER_MODEL:           # least recently used shape first
             old = slots.pop(live.pop(0))
-            if old.busy:                                    # (its run is still going: leave it alone, take no slot)
+            if old.busy:                                    # (its run is still going: leave it alone, take none)
                 slots[key] = _Volatile(wkey)
                 return None
             old.drop_graphs()
-        slot = _GraphSlot(x, num_classes, max(GRAPH_SLOT_MIN_ITERS, n_iter), wkey)
-    slots[key] = slot
-    return slot
+        own = _RunBuffers(x, num_classes, max(GRAPH_SLOT_MIN_ITERS, n_iter), wkey)
+    slots[key] = own
+    return own
 
 
 def release_graph_cache(model=None):
     """drop the cached graph pairs (and the several GB of activations their pools hold) of ``model``, or of every model"""
     for m in ([model] if model is not None else list(_GRAPH_SLOTS.keys())):
         for slot in _GRAPH_SLOTS.pop(m, {}).values():
-            if isinstance(slot, _GraphSlot):
+            if isinstance(slot, _RunBuffers):
                 slot.drop_graphs()
+
+
+def _owned(name):
+    return property(lambda self: getattr(self.own, name))
 
 
 class ApgdRun:
     """One APGD run as an object: ``start()`` is step 0 (reference lines 342-383), ``step(i)`` is loop
     iteration i (lines 385-569).  ``apgd_train`` drives it; bench.py times ``step`` directly.
-    Nothing in ``step`` synchronises with the host."""
+    Nothing in ``step`` synchronises with the host.
+
+    Every device buffer and all graph state belong to ``self.own``, the run's one ``_RunBuffers``: the model's cached one
+    when the run is eligible (graph mode, contiguous input, weights that held still, not in use), else a private one.  ``x``
+    and ``x_start`` are copied in and never written; ``result()`` hands out copies.  ``release_graphs()`` ends the run: a
+    cached owner keeps its pair for the next run, a private one drops it; the buffers stay readable either way."""
+
+    x, grad, pred, pred_best, st, ws, n_ignored, graphs = (_owned(k) for k in (
+        "x", "grad", "pred", "pred_best", "st", "ws", "n_ignored", "graphs"))
 
     def __init__(self, model, x, y, eps, n_iter, loss, track_loss, early_stop, num_classes, weights, x_start,
                  fuse_upsample=None, norm="Linf"):
@@ -487,119 +524,80 @@ class ApgdRun:
         self.tmode = N.MODE_BY_NAME[track_loss] if track_loss is not None else self.mode
         self.eps, self.n_iter, self.early_stop, self.num_classes = float(eps), n_iter, early_stop, num_classes
         self.y = y
-        device = x.device
-        B = x.shape[0]
-        self.B, self.HW = B, x.shape[-2] * x.shape[-1]
+        self.B, self.HW = x.shape[0], x.shape[-2] * x.shape[-1]
         self.yc = compact_labels(y, num_classes)
         self.w = None
         if weights is not None and (self.mode == 1 or self.tmode == 1):
-            self.w = weights.to(device=device, dtype=torch.float32).contiguous()
+            self.w = weights.to(device=x.device, dtype=torch.float32).contiguous()
         self.cps = apgd_checkpoints(n_iter)
         self.gscale = 1.0 / float(self.HW)
         self.defer = True      # K7 sums K2's per-block records itself (no finalize launch); off when verbose
-        self.ws_low = None
         self.last = None       # K2 outputs of the latest iterate
         self.k2_events = None  # optional list of (start, end) event pairs, one per step (bench.py)
         # (capture costs ~3 eager iterations; the L2 step -- on no shipped entry point, SURVEY fact 2 -- keeps the eager loop)
-        self.use_graph = USE_HIP_GRAPH and n_iter >= GRAPH_MIN_ITER and norm == "Linf"
-        self.graphs = None
-        self._g_xin = self._g_logits = self._ws_pin = None
+        self.use_graph = USE_HIP_GRAPH and n_iter >= GRAPH_MIN_ITER and n_iter > 3 and norm == "Linf"
+        self._gs = _capture_stream(x.device)
         self._caller_stream = None
-        self._first_graph_step = 2   # iterations 0 and 1 of a capturing run are eager (library warm-up on the capture stream)
-        # graph mode with a slot: every buffer a captured graph addresses belongs to the slot (and to the next run after this
-        # one); the caller's tensors are copied in, the results are copied out (``result``)
-        graph_mode = self.use_graph and n_iter > 3
-        self.slot = _graph_slot(model, x, num_classes, n_iter) if (graph_mode and x.is_contiguous()) else None
-        if self.slot is not None:
-            sl = self.slot
-            sl.busy = True
-            # A run that finds the pair already captured replays it from iteration 0 (the in-place K1 takes a = 1 there from
-            # the device-side loop index): its iterate starts in the buffer the pair addresses as x_adv, bufs[1] -- where
-            # the two eager warm-up iterations of the capturing run had rotated it to
-            self._first_graph_step = 0 if sl.graphs is not None else 2
-            k = 1 if sl.graphs is not None else 0
-            sl.x.copy_(x)
-            sl.bufs[k].copy_(x_start)
-            self.x, self.x_adv = sl.x, sl.bufs[k]
-            self._gs = _capture_stream(device)
-            self.n_ignored = N.count_ignored(self.yc, out=sl.n_ignored)
-            sl.reset(self.eps, n_iter, self.cps)
-            self.st, self.pred, self.stats, self.ws, self.dlogits = sl.st, sl.pred, sl.stats, sl.ws, sl.dlogits
-            self.graphs, self._g_xin, self._g_logits, self._ws_pin = sl.graphs, sl.g_xin, sl.g_logits, sl.ws_pin
-        else:
-            self.x = x
-            self.x_adv = x_start
-            self.n_ignored = N.count_ignored(self.yc)
-            self.st = ApgdState(B, n_iter, self.eps, device)
-            pred_dtype = torch.uint8 if num_classes <= 255 else torch.int16
-            self.pred = torch.empty(B, x.shape[-2], x.shape[-1], dtype=pred_dtype, device=device)
-            self.stats = (torch.empty(B, dtype=torch.float32, device=device),
-                          torch.empty(B, dtype=torch.float32, device=device),
-                          torch.empty(B, dtype=torch.int32, device=device))
-            self.ws = N.loss_workspace(B, self.HW, device)
-            self.dlogits = None
+        own = _graph_slot(model, x, num_classes, n_iter, self.fused) if (self.use_graph and x.is_contiguous()) else None
+        self._private = own is None
+        self.own = own = _RunBuffers(x, num_classes, max(n_iter, 1)) if own is None else own
+        # A run that finds the pair already captured replays it from iteration 0 (the in-place K1 takes a = 1 there from the
+        # device-side loop index): its iterate starts in the buffer the pair addresses as x_adv, bufs[1] -- where the two
+        # eager iterations of the capturing run (library warm-up on the capture stream) had rotated it to
+        self._first_graph_step, k = (0, 1) if own.graphs is not None else (2, 0)
+        self.x_adv, self.x_old, self.x_next = (own.bufs[(k + j) % 3] for j in range(3))
+        own.x.copy_(x)
+        self.x_adv.copy_(x_start)
+        N.count_ignored(self.yc, out=own.n_ignored)
+        own.reset(self.eps, n_iter, self.cps)
+        own.busy = True        # last: a constructor that raises leaves a cached owner free for the next run
 
     def _loss(self, logits, want_grad):
+        o = self.own
         ev = None
         if self.k2_events is not None:
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             ev[0].record()
         if self.fused:
-            if self.ws_low is None:
-                self.ws_low = torch.empty(N.lib().sea_loss_upsampled_workspace_bytes(
-                    self.B, logits.shape[1], logits.shape[2], logits.shape[3], self.x.shape[-2], self.x.shape[-1]),
-                    dtype=torch.uint8, device=logits.device)
             r = N.loss_fwd_bwd_upsampled(logits.detach().contiguous(), self.yc, self.w, self.mode, self.tmode,
-                                         self.gscale, want_grad=want_grad, pred=self.pred, workspace=self.ws_low,
-                                         out=self.stats, dlow=self.dlogits if want_grad else None)
+                                         self.gscale, want_grad=want_grad, pred=o.pred, workspace=o.k2u_workspace(logits),
+                                         out=o.stats, dlow=o.dlogits if want_grad else None)
         else:
             r = N.loss_fwd_bwd(logits.detach(), self.yc, self.w, self.mode, self.tmode, self.gscale,
-                               want_grad=want_grad, pred=self.pred, workspace=self.ws, out=self.stats,
-                               dlogits=self.dlogits if want_grad else None, defer=self.defer)
+                               want_grad=want_grad, pred=o.pred, workspace=o.ws, out=o.stats,
+                               dlogits=o.dlogits if want_grad else None, defer=self.defer)
         if ev is not None:
             ev[1].record()
             self.k2_events.append(ev)
         if want_grad:
-            self.dlogits = r["dlogits"]
-            if self.slot is not None:
-                self.slot.dlogits = self.dlogits
+            o.keep_k2_grad(r["dlogits"])
         self.last = r
         return r
 
+    def _select(self):
+        o = self.own
+        N.select_copy(o.st.flags, self.x_adv, o.grad, o.x_best, o.grad_best, o.x_best_adv, o.pred, o.pred_best)
+
     def start(self):
+        o = self.own
         x_in, logits = _forward_logits(self.model, self.x_adv, True, self.fused)
         r = self._loss(logits, True)
         g = _input_grad(logits, x_in, r["dlogits"])
         del logits
-        N.apgd_track(r, self.n_ignored, self.HW, 0, max(self.n_iter, 1), 0, False, True, self.st)
-        if self.slot is not None:
-            sl = self.slot
-            self.grad = sl.grad.copy_(g)
-            self.pred_best = sl.pred_best.copy_(self.pred)
-            self.x_best = sl.x_best.copy_(self.x_adv)
-            self.x_best_adv = sl.x_best_adv.copy_(self.x_adv)
-            self.grad_best = sl.grad_best.copy_(g)
-            if self._first_graph_step == 0:
-                self.x_old, self.x_next = sl.bufs[2].copy_(self.x_adv), sl.bufs[0]
-            else:
-                self.x_old, self.x_next = sl.bufs[1].copy_(self.x_adv), sl.bufs[2]
-            return
-        self.grad = g
-        self.pred_best = self.pred.clone()
-        self.x_best = self.x_adv.clone()
-        self.x_best_adv = self.x_adv.clone()
-        self.grad_best = self.grad.clone()
-        self.x_old = self.x_adv.clone()
-        self.x_next = torch.empty_like(self.x_adv)
+        N.apgd_track(r, o.n_ignored, self.HW, 0, max(self.n_iter, 1), 0, False, True, o.st)
+        o.grad.copy_(g)
+        o.grad_best.copy_(g)
+        o.pred_best.copy_(o.pred)
+        for t in (o.x_best, o.x_best_adv, self.x_old):
+            t.copy_(self.x_adv)
 
     def step(self, i: int):
-        if self.use_graph and self.n_iter > 3:
+        if self.use_graph:
             if self._first_graph_step <= i < self.n_iter - 1:
                 return self._step_graph(i)
             if i == 1:
                 # eager, but on the stream the graphs will be captured on: per-stream library state (MIOpen / hipBLASLt
                 # handles and workspaces) must exist before a capture starts
-                self._gs = _capture_stream(self.x.device)
                 cur = torch.cuda.current_stream()
                 self._gs.wait_stream(cur)
                 with torch.cuda.stream(self._gs):
@@ -609,28 +607,26 @@ class ApgdRun:
         self._step_eager(i)
 
     def _step_eager(self, i: int):
+        o = self.own
         # ---- gradient step (reference lines 389-456): K1, then rotate the three iterate buffers
         a = 0.75 if i > 0 else 1.0
         if self.norm == "L2":
             if self._l2_ws is None:
-                self._l2_ws = torch.empty(N.lib().sea_apgd_l2_workspace_bytes(self.B) // 8, dtype=torch.float64, device=self.x.device)
-            N.apgd_l2_step(self.x, self.x_adv, self.x_old, self.grad, self.st.step, self.eps, a, out=self.x_next,
-                           workspace=self._l2_ws)
+                self._l2_ws = torch.empty(N.lib().sea_apgd_l2_workspace_bytes(self.B) // 8, dtype=torch.float64, device=o.x.device)
+            N.apgd_l2_step(o.x, self.x_adv, self.x_old, o.grad, o.st.step, self.eps, a, out=self.x_next, workspace=self._l2_ws)
         else:
-            N.apgd_linf_step(self.x, self.x_adv, self.x_old, self.grad, self.st.step, self.eps, a, out=self.x_next)
+            N.apgd_linf_step(o.x, self.x_adv, self.x_old, o.grad, o.st.step, self.eps, a, out=self.x_next)
         self.x_old, self.x_adv, self.x_next = self.x_adv, self.x_next, self.x_old
         # ---- model forward, fused loss/grad/track/acc/argmax (K2), model input-gradient
         want = i < self.n_iter - 1  # the reference skips the last backward (line 467)
         x_in, logits = _forward_logits(self.model, self.x_adv, want, self.fused)
         r = self._loss(logits, want)
         if want:
-            g = _input_grad(logits, x_in, r["dlogits"])
-            self.grad = g if self.slot is None else self.grad.copy_(g)
+            o.grad.copy_(_input_grad(logits, x_in, r["dlogits"]))   # the gradient buffer keeps its address (K1 / K4 read it)
         del logits
         # ---- bookkeeping on the device (K7 decisions, K4 copies)
-        N.apgd_track(r, self.n_ignored, self.HW, i, self.n_iter, self.cps.get(i, 0), self.early_stop, False, self.st)
-        N.select_copy(self.st.flags, self.x_adv, self.grad, self.x_best, self.grad_best, self.x_best_adv, self.pred,
-                      self.pred_best)
+        N.apgd_track(r, o.n_ignored, self.HW, i, self.n_iter, self.cps.get(i, 0), self.early_stop, False, o.st)
+        self._select()
 
     # ---- HIP-graph mode ----------------------------------------------------------------------------------------
     # An iteration is ~360 kernel launches that the host needs 9-14 ms to enqueue (ConvNeXt-T, B=8) for 22 ms of GPU
@@ -641,18 +637,13 @@ class ApgdRun:
     #     graph B = input-gradient backward + K7 (loop index / checkpoint window from device memory) + K4
     # Iterations 0 and 1 run eagerly (library warm-up on the capture stream), the last one too (no backward there).
     # Same kernels, same arithmetic, same order: the outputs are bitwise those of the eager loop (tested).
-    def _graph_ready(self):
-        return self.graphs is not None
-
     def _graph_failed(self, exc):
         """A model whose forward / backward cannot be captured (a host sync such as .item(), a library that allocates or
         JIT-compiles on first use of a shape, ...) keeps working: the run continues with the eager loop, which is the same
         kernels in the same order.  Reported once per run on stderr."""
         import sys
-        self.use_graph, self.graphs = False, None
-        self._g_xin = self._g_logits = None
-        if self.slot is not None:
-            self.slot.drop_graphs()
+        self.use_graph = False
+        self.own.drop_graphs()
         # torch.cuda.graph.__exit__ does not leave its stream context when capture_end() itself raises (an invalidated
         # capture): put the caller's stream back
         torch.cuda.set_stream(self._caller_stream)
@@ -662,86 +653,70 @@ class ApgdRun:
 
     def _capture(self, i: int):
         """captures the two graphs AND performs iteration i; falls back to the eager loop when a capture fails"""
-        dev = self.x.device
+        o = self.own
         self._caller_stream = torch.cuda.current_stream()
-        if self.slot is not None:      # radius, run length, checkpoint table: device words of the slot (set by slot.reset)
-            self.it_dev, self.cp_dev = self.slot.it_dev.fill_(i), self.slot.cp_dev
-            eps_arg, n_iter_arg = self.slot.eps_dev, self.slot.niter_dev
-        else:
-            self.it_dev = torch.full((1,), i, dtype=torch.int32, device=dev)
-            tab = [self.cps.get(k, 0) for k in range(max(self.n_iter, 1))]
-            self.cp_dev = torch.tensor(tab, dtype=torch.int32, device=dev)
-            eps_arg, n_iter_arg = self.eps, self.n_iter
+        o.it_dev.fill_(i)          # radius, run length, checkpoint table: device words too (set by o.reset)
         ga, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         try:
             with torch.cuda.graph(ga, stream=self._gs):
-                N.apgd_linf_step_graph(self.x, self.x_adv, self.x_old, self.grad, self.st.step, eps_arg, self.it_dev)
-                self._g_xin, self._g_logits = _forward_logits(self.model, self.x_adv, True, self.fused)
+                N.apgd_linf_step_graph(o.x, self.x_adv, self.x_old, o.grad, o.st.step, o.eps_dev, o.it_dev)
+                g_xin, g_logits = _forward_logits(self.model, self.x_adv, True, self.fused)
         except Exception as exc:   # nothing of iteration i has run yet (a capture executes nothing)
             self._graph_failed(exc)
             return self._step_eager(i)
         ga.replay()
-        r = self._loss(self._g_logits, True)          # eager, and it defines the (persistent) K2 output buffers
+        r = self._loss(g_logits, True)                # eager, and it defines the (persistent) K2 output buffers
         try:
             with torch.cuda.graph(gb, pool=ga.pool(), stream=self._gs):
-                g = _input_grad(self._g_logits, self._g_xin, r["dlogits"])
-                self.grad.copy_(g)                           # the gradient buffer keeps its address (K1 / K4 read it)
-                N.apgd_track_graph(r, self.n_ignored, self.HW, self.it_dev, self.cp_dev, n_iter_arg, self.early_stop, self.st)
-                N.select_copy(self.st.flags, self.x_adv, self.grad, self.x_best, self.grad_best, self.x_best_adv, self.pred,
-                              self.pred_best)
+                o.grad.copy_(_input_grad(g_logits, g_xin, r["dlogits"]))
+                N.apgd_track_graph(r, o.n_ignored, self.HW, o.it_dev, o.cp_dev, o.niter_dev, self.early_stop, o.st)
+                self._select()
         except Exception as exc:   # K1 of iteration i is done (graph A replayed, in place): finish the iteration eagerly.
             # The failed capture has consumed the autograd graph of graph A's forward, so the forward is run again, on the
             # updated iterate (same kernels, same bits)
             self._graph_failed(exc)
+            del g_xin, g_logits
             x_in, logits = _forward_logits(self.model, self.x_adv, True, self.fused)
             r = self._loss(logits, True)
-            self.grad.copy_(_input_grad(logits, x_in, r["dlogits"]))
+            o.grad.copy_(_input_grad(logits, x_in, r["dlogits"]))
             del logits
-            N.apgd_track(r, self.n_ignored, self.HW, i, self.n_iter, self.cps.get(i, 0), self.early_stop, False, self.st)
-            N.select_copy(self.st.flags, self.x_adv, self.grad, self.x_best, self.grad_best, self.x_best_adv, self.pred,
-                          self.pred_best)
+            N.apgd_track(r, o.n_ignored, self.HW, i, self.n_iter, self.cps.get(i, 0), self.early_stop, False, o.st)
+            self._select()
             return
         gb.replay()
-        self.graphs = (ga, gb)
-        # the graphs bake in the address of the split-K workspace the model's GEMMs used: keep it alive while they may replay
-        self._ws_pin = N.ksplit_workspace_pin(dev)
-        if self.slot is not None:
-            sl = self.slot
-            sl.graphs, sl.sig, sl.ws_pin = self.graphs, self._graph_sig(), self._ws_pin
-            sl.g_xin, sl.g_logits = self._g_xin, self._g_logits
+        o.keep_graphs((ga, gb), self._graph_sig(), g_xin, g_logits)
 
     def _graph_sig(self):
         """what a captured pair bakes in besides addresses and weights: K7's early-stop flag, where it finds K2's sums, and
         the process-global arithmetic state of the model's forward / backward (``_arith_signature``)"""
-        return (bool(self.early_stop), bool(self.defer), bool(self.fused), _arith_signature(self.model))
+        return (bool(self.early_stop), bool(self.defer), _arith_signature(self.model))
 
     def _step_graph(self, i: int):
-        if self.graphs is not None and self.slot is not None and i == self._first_graph_step:
-            if self.slot.sig != self._graph_sig():        # (a verbose run after a silent one: capture again)
-                self.slot.drop_graphs()
-                self.graphs = self._g_xin = self._g_logits = None
+        o = self.own
+        if o.graphs is not None and i == self._first_graph_step:
+            if o.sig != self._graph_sig():                # (a verbose run after a silent one: capture again)
+                o.drop_graphs()
             else:
-                self.slot.it_dev.fill_(i)                 # the loop index of the pair's first replay in THIS run
-        if self.graphs is None:
+                o.it_dev.fill_(i)                         # the loop index of the pair's first replay in THIS run
+        if o.graphs is None:
             self._capture(i)                              # captures AND performs iteration i
             return
-        self.graphs[0].replay()
-        self._loss(self._g_logits, True)
-        self.graphs[1].replay()
+        o.graphs[0].replay()
+        self._loss(o.g_logits, True)
+        o.graphs[1].replay()
 
     def release_graphs(self):
-        """drop the captured graphs and the activations their private pool keeps alive (a run holds several GB of them at
-        B=8, 512x512; an evaluation creates three runs per batch and attack)"""
-        self.graphs = None
-        self._g_xin = self._g_logits = None
-        self._ws_pin = None
-        if self.slot is not None:           # the pair stays with the slot for the next run; the slot is free again
-            self.slot.busy = False
+        """the run is over.  A private owner drops its captured graphs and the activations their pool keeps alive (several GB
+        at B=8, 512x512; an evaluation creates three runs per batch and attack); a cached one keeps them for the next run and
+        is free again.  The buffers stay readable."""
+        if self._private:
+            self.own.drop_graphs()
+        self.own.busy = False
 
     def result(self):
-        if self.slot is not None:           # the slot's buffers belong to the next run: hand out copies
-            return self.x_best.clone(), self.st.acc.clone(), self.st.loss_best.clone(), self.x_best_adv.clone()
-        return self.x_best, self.st.acc, self.st.loss_best, self.x_best_adv
+        """copies: the buffers belong to the owner, and a cached owner to the next run"""
+        o = self.own
+        return o.x_best.clone(), o.st.acc.clone(), o.st.loss_best.clone(), o.x_best_adv.clone()
 
 
 def apgd_train(model, x, y, norm, eps, n_iter=10, use_rs=False, loss="ce", verbose=False, is_train=False,
@@ -783,17 +758,19 @@ def apgd_train(model, x, y, norm, eps, n_iter=10, use_rs=False, loss="ce", verbo
         x_adv = x_init.detach().clone().contiguous().float()
     x_adv = x_adv.clamp_(0.0, 1.0)
 
-    run = ApgdRun(model, x, y, eps, n_iter, loss, track_loss, early_stop, num_classes, weights, x_adv, norm=norm)
-    run.defer = not verbose  # the verbose log line reads the per-image sums on the host
-    if logger is not None:
-        # reference lines 302-306 log this whenever ignore labels exist (one host read per run, outside the loop)
-        n_ign = int(run.n_ignored.sum())
-        if n_ign > 0:
-            logger.log(f"{n_ign / y.numel():.2%} pixels are masked out.")
+    run = None
     try:
+        run = ApgdRun(model, x, y, eps, n_iter, loss, track_loss, early_stop, num_classes, weights, x_adv, norm=norm)
+        run.defer = not verbose  # the verbose log line reads the per-image sums on the host
+        if logger is not None:
+            # reference lines 302-306 log this whenever ignore labels exist (one host read per run, outside the loop)
+            n_ign = int(run.n_ignored.sum())
+            if n_ign > 0:
+                logger.log(f"{n_ign / y.numel():.2%} pixels are masked out.")
         return _apgd_drive(run, y, n_iter, verbose, logger, early_stop, poll_every, num_classes, return_pred)
     finally:
-        run.release_graphs()            # (also when a step raises: the slot must not stay busy)
+        if run is not None:
+            run.release_graphs()        # (also when the logging or a step raises: a cached owner must not stay busy)
 
 
 def _apgd_drive(run, y, n_iter, verbose, logger, early_stop, poll_every, num_classes, return_pred):
@@ -827,7 +804,7 @@ def _apgd_drive(run, y, n_iter, verbose, logger, early_stop, poll_every, num_cla
                 done_evt.record()
     out = run.result()
     if return_pred:
-        out = out + ((run.pred_best.clone() if run.slot is not None else run.pred_best),)
+        out = out + (run.pred_best.clone(),)
     return out
 
 

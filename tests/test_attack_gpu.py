@@ -261,6 +261,45 @@ def test_hip_graph_replay_with_the_fused_upsample_loss_is_bitwise_the_eager_loop
     torch.testing.assert_close(runs["graph"][2], runs["unfused"][2], rtol=2e-2, atol=1e-3)
 
 
+def test_fused_and_unfused_runs_of_one_shape_share_no_cached_buffers():
+    """K2u writes a low-resolution logit gradient, K2 a full-resolution one, and a captured pair replays one of the two
+    forwards: the cached owner of a run's buffers is keyed by the loss kernel as well.  Fused -> unfused -> fused on one
+    model and shape WITHOUT releasing the graph cache in between (same 151-class UperNet-ConvNeXt-T as above): every result
+    bit-identical to the same mode's result taken with the cache released first."""
+    from semseg import attacker as A
+    from semseg.models import UperNetForSemanticSegmentation
+    from semseg.utils.utils import ADE_WTS
+    torch.manual_seed(0)
+    model = UperNetForSemanticSegmentation("ConvNeXt-T_CVST", 151, None).eval().cuda()
+    x = torch.rand(2, 3, 512, 512, generator=torch.Generator().manual_seed(5)).cuda()
+    with torch.no_grad():
+        y = model(x).max(1)[1]
+    y[0, :4] = -1
+    w = torch.tensor(ADE_WTS).cuda()[:151]
+    noise = torch.rand(x.shape, generator=torch.Generator().manual_seed(6)).cuda()
+
+    def attack(fuse):
+        A.FUSE_UPSAMPLE = fuse
+        return A.apgd_train(model, x, y, "Linf", 8.0 / 255, n_iter=20, use_rs=True, loss="mask-ce-bal", early_stop=True,
+                            track_loss="ce-avg", num_classes=151, weights=w, noise=noise, return_pred=True)
+
+    old = (A.USE_HIP_GRAPH, A.FUSE_UPSAMPLE)
+    try:
+        A.USE_HIP_GRAPH = True
+        alone = {}
+        for fuse in ("auto", False):
+            A.release_graph_cache(model)
+            alone[fuse] = attack(fuse)
+        A.release_graph_cache(model)
+        mixed = [(fuse, attack(fuse)) for fuse in ("auto", False, "auto")]
+    finally:
+        A.USE_HIP_GRAPH, A.FUSE_UPSAMPLE = old
+        A.release_graph_cache(model)
+    for fuse, out in mixed:
+        for a, b in zip(alone[fuse], out):
+            assert torch.equal(a, b), f"fuse_upsample={fuse!r} after a run of the other mode"
+
+
 @pytest.mark.parametrize("where", ["forward", "backward"])
 def test_hip_graph_capture_failure_falls_back_to_the_eager_loop(where, capfd):
     """A model that cannot be captured (a host synchronisation inside its forward, or inside its backward) must keep

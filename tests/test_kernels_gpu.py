@@ -69,6 +69,66 @@ def test_linf_kernels_vs_oracle(N, shape):
     assert torch.equal(d.cpu(), dref) and torch.equal(xin.cpu(), x + dref)
 
 
+@pytest.mark.parametrize("hw", [(9, 7), (8, 8)])     # 3*H*W odd: one float per lane; a multiple of four: float4
+def test_replayable_k1_k7_with_scalar_arguments_and_with_device_words_agree(N, hw):
+    """The replayable K1 / K7 of the HIP-graph mode (loop index and checkpoint table in device memory) come in two forms:
+    radius and run length as launch arguments (sea_apgd_linf_step_graph / sea_apgd_track_graph), or as device words too
+    (the _dev pair, which ApgdRun captures; its tables are sized for the longest run replayed).  The same seeded buffers go
+    through both for five iterations of a 12-step schedule -- a = 1 at iteration 0, the window-2 checkpoint at iteration 1
+    with one image that halves its step and restarts and one that does not -- and every output buffer is bit-identical
+    after every iteration."""
+    from semseg import attacker as A
+    (H, W), B, n_iter, cap, eps, steps = hw, 3, 12, 16, 8.0 / 255, 5
+    HW = H * W
+    cps = A.apgd_checkpoints(n_iter)
+    assert cps[1] == 2 and 0 not in cps
+    g = torch.Generator().manual_seed(41 + W)
+    x = torch.rand(B, 3, H, W, generator=g)
+    x0 = (x + eps * (2 * torch.rand(x.shape, generator=g) - 1)).clamp(0, 1)
+    grads = [torch.randn(x.shape, generator=g) for _ in range(steps + 1)]
+    preds = [torch.randint(0, 21, (B, H, W), generator=g).to(torch.uint8) for _ in range(steps + 1)]
+    # tracking-loss sums per image: image 0 rises (no halving at the checkpoint), image 1 falls (halved, restart), image 2 random
+    tracks = [torch.tensor([10.0 + i, 10.0 - i, 20.0 * float(torch.rand(1, generator=g))]) for i in range(steps + 1)]
+    corr = [torch.randint(0, HW - 4, (B,), generator=g).to(torch.int32) for _ in range(steps + 1)]
+    n_ign = torch.tensor([0, 3, 4], dtype=torch.int32).cuda()
+
+    def drive(device_words):
+        rows = cap if device_words else n_iter
+        st = A.ApgdState(B, rows, eps, "cuda")
+        b = dict(x_adv=x0.cuda(), x_old=x0.cuda(), grad=grads[0].cuda(), x_best=x0.cuda(), x_best_adv=x0.cuda(),
+                 grad_best=grads[0].cuda(), pred=preds[0].cuda(), pred_best=preds[0].cuda(),
+                 it_dev=torch.zeros(1, dtype=torch.int32, device="cuda"))
+        stats = lambda i: dict(loss_sum=tracks[i].cuda(), track_sum=tracks[i].cuda(), n_correct=corr[i].cuda())  # noqa: E731
+        N.apgd_track(stats(0), n_ign, HW, 0, n_iter, 0, True, True, st)       # step 0 of a run
+        tab = torch.zeros(rows, dtype=torch.int32)
+        for k, v in cps.items():
+            tab[k] = v
+        tab, xd = tab.cuda(), x.cuda()
+        eps_arg = torch.full((1,), eps, dtype=torch.float32, device="cuda") if device_words else eps
+        n_arg = torch.full((1,), n_iter, dtype=torch.int32, device="cuda") if device_words else n_iter
+        snaps = []
+        for i in range(steps):
+            N.apgd_linf_step_graph(xd, b["x_adv"], b["x_old"], b["grad"], st.step, eps_arg, b["it_dev"])
+            b["grad"].copy_(grads[i + 1])                                   # (what the model's backward would leave)
+            b["pred"].copy_(preds[i + 1])
+            N.apgd_track_graph(stats(i + 1), n_ign, HW, b["it_dev"], tab, n_arg, True, st)
+            N.select_copy(st.flags, b["x_adv"], b["grad"], b["x_best"], b["grad_best"], b["x_best_adv"], b["pred"], b["pred_best"])
+            snap = {k: v.clone() for k, v in b.items()}
+            snap.update({k: getattr(st, k).clone() for k in ("acc_cnt", "acc", "loss_best", "loss_best_last", "reduced_last",
+                                                             "step", "flags", "done")})
+            snap["loss_steps"] = st.loss_steps[:n_iter].clone()
+            snaps.append(snap)
+        return snaps
+
+    scalar, words = drive(False), drive(True)
+    for i, (s, d) in enumerate(zip(scalar, words)):
+        for k in s:
+            assert torch.equal(s[k], d[k]), (i, k)
+    last = scalar[-1]
+    assert int(last["it_dev"]) == steps and not torch.equal(last["x_adv"], x0.cuda())
+    assert last["step"][1] < last["step"][0] == scalar[0]["step"][0]          # image 1 was halved, image 0 never
+
+
 # ------------------------------------------------------------------------------------------------ K2
 MODES = (("mask_ce_avg", 0), ("mask_ce_bal", 1), ("js_avg", 2), ("ce", 3))
 
