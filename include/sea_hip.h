@@ -637,6 +637,35 @@ int sea_bn_train_bwd(const float* g, const float* x, const float* y, const float
                      const float* scale, float* dx, float* dgamma, float* dbeta, float* gr, float* work, int64_t M, int C,
                      int relu, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * T2: the training criteria of the PIR-AT outer step, CrossEntropy and OhemCrossEntropy of the reference's
+ * semseg/losses.py:6-63, forward + hard-pixel selection + backward on the device.  logits: dense NCHW (B, C, H*W),
+ * SEA_DTYPE_F32 or SEA_DTYPE_BF16; y: int64 labels (B, H*W) as the data loader hands them over; ignore_label: any
+ * integer; w: C class weights or NULL.  A label outside [0, C) other than ignore_label is treated as ignored and sets
+ * the error word.  B*H*W < 2^31.  No float atomics: bitwise reproducible.  Nothing is read by the host.
+ * `words`: 64 bytes of device memory, ZEROED by the caller before sea_train_ce_fwd, 8-byte aligned:
+ *   double sum_sel, sum_w, sum_loss; float loss, coef; uint32 t_bits; int32 take, n_sel, n_valid, n_hard, n_min, mode,
+ *   err  (loss: the criterion's value; coef: 1/sum_w or 1/n_sel; mode: 0 threshold, 1 top-k; semseg/losses.py:48-55).
+ * sea_train_ce_workspace_bytes: bytes of `workspace` (16-byte aligned) that the calls below need.
+ * sea_train_ce_fwd: per pixel w[y]*(lse - z_y), 0 where ignored, into loss_px (B*H*W floats); per-block records
+ *   {sum loss, sum w[y], sum of losses > thresh, n_valid, n_hard}, then their fixed-order sum in double.  reduce_mean
+ *   = 1 (nn.CrossEntropyLoss, losses.py:15-19): loss = sum loss / sum w[y].  reduce_mean = 0 (losses.py:48-52): n_min =
+ *   n_valid / 16 and the regime; in threshold mode (n_hard >= n_min) also the final words.
+ * sea_train_ohem_select (after sea_train_ce_fwd with reduce_mean = 0, same workspace and words): in top-k mode the
+ *   n_min-th largest loss t by a radix select over the float bits (four byte-histogram passes), the sum of the losses
+ *   above t plus `take` ties at t (taken in ascending flat pixel index), the words (losses.py:53-55); in both modes the
+ *   loss of every pixel that is not selected is overwritten with -1 in loss_px.  n_sel = 0 gives loss = NaN.
+ * sea_train_ce_bwd: dlogits = g[0] * coef * w[y] * (softmax(z) - onehot(y)) at valid (ohem = 1: selected) pixels, 0
+ *   elsewhere, in the logits' dtype; g: the upstream gradient, one float in device memory. */
+size_t sea_train_ce_workspace_bytes(int B, int64_t HW);
+int sea_train_ce_fwd(const void* logits, int dtype, const int64_t* y, const float* w, int64_t ignore_label, float thresh,
+                     int reduce_mean, int B, int C, int64_t HW, float* loss_px, void* workspace, size_t workspace_bytes,
+                     void* words, void* stream);
+int sea_train_ohem_select(float* loss_px, int64_t N, void* workspace, size_t workspace_bytes, void* words, void* stream);
+int sea_train_ce_bwd(const void* logits, int dtype, const int64_t* y, const float* w, int64_t ignore_label, int ohem,
+                     int B, int C, int64_t HW, const float* loss_px, const float* g, const void* words, void* dlogits,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,7 @@ SOURCES = [
     ("msf_kernels.hip", ["-ffp-contract=off"]),
     ("psp_kernels.hip", []),
     ("bn_train.hip", []),
+    ("train_loss.hip", []),
     ("greedy_host.cpp", ["-ffp-contract=off"]),
     ("api_misc.cpp", []),
 ]

@@ -125,6 +125,10 @@ _SIGS = {
     "sea_bn_train_workspace_floats": (_i64, [_i64, _i]),
     "sea_bn_train_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _f, _f, _i, _vp]),
     "sea_bn_train_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _vp]),
+    "sea_train_ce_workspace_bytes": (_sz, [_i, _i64]),
+    "sea_train_ce_fwd": (_i, [_vp, _i, _vp, _vp, _i64, _f, _i, _i, _i, _i64, _vp, _vp, _sz, _vp, _vp]),
+    "sea_train_ohem_select": (_i, [_vp, _i64, _vp, _sz, _vp, _vp]),
+    "sea_train_ce_bwd": (_i, [_vp, _i, _vp, _vp, _i64, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -336,6 +340,72 @@ def loss_fwd_bwd_upsampled(low, y, weights, mode: int, track_mode: int, grad_sca
                                         _p(workspace), workspace.numel(), _p(out[0]), _p(out[1]), _p(out[2]),
                                         _stream()), "sea_loss_fwd_bwd_upsampled")
     return dict(dlogits=dlow, loss_sum=out[0], track_sum=out[1], n_correct=out[2], pred=pred)
+
+
+# ------------------------------------------------------------------------------------------------ T2
+# the 64 bytes of device words of the training criterion (include/sea_hip.h), as a float64[8] tensor: int32 / float32
+# views give the fields below
+TRAIN_WORDS_F32 = {"loss": 6, "coef": 7}
+TRAIN_WORDS_I32 = {"t_bits": 8, "take": 9, "n_sel": 10, "n_valid": 11, "n_hard": 12, "n_min": 13, "mode": 14, "err": 15}
+
+
+def train_words_dict(words: torch.Tensor) -> dict:
+    """Host copy of the device words (debugging and tests ONLY: this synchronises)."""
+    f, i, d = words.view(torch.float32).cpu(), words.view(torch.int32).cpu(), words.cpu()
+    out = {k: float(f[j]) for k, j in TRAIN_WORDS_F32.items()}
+    out.update({k: int(i[j]) for k, j in TRAIN_WORDS_I32.items()})
+    out.update(sum_sel=float(d[0]), sum_w=float(d[1]), sum_loss=float(d[2]))
+    out["t"] = float(i[8:9].view(torch.float32)[0])
+    return out
+
+
+def _train_args(logits, y, weight):
+    _dev(logits, y, weight)
+    if logits.dim() != 4 or not logits.is_contiguous():
+        raise SeaNativeError("the training criterion takes dense NCHW logits (B,C,H,W); channels_last has no T2 kernel")
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise SeaNativeError(f"the training criterion takes float32 or bfloat16 logits, got {logits.dtype}")
+    B, Cc, H, W = logits.shape
+    if y.dtype != torch.int64 or y.shape != (B, H, W) or not y.is_contiguous():
+        raise SeaNativeError("labels must be a contiguous int64 (B,H,W) tensor")
+    if weight is not None:
+        weight = _f32c(weight)
+        if weight.numel() != Cc:
+            raise SeaNativeError("class weights must have C entries")
+    return B, Cc, H * W, weight
+
+
+def train_ce_forward(logits, y, weight, ignore_label: int, thresh: float = 0.0, ohem: bool = False):
+    """T2 forward (+ the OHEM select).  Returns (loss, loss_px, words): the 0-dim fp32 loss, the
+    per-pixel loss plane the backward needs and the device words (loss: a copy of its word).  Nothing is read by the host."""
+    B, Cc, HW, weight = _train_args(logits, y, weight)
+    dev = logits.device
+    L = lib()
+    nb = L.sea_train_ce_workspace_bytes(B, HW)
+    workspace = torch.empty(nb, dtype=torch.uint8, device=dev)
+    words = torch.zeros(8, dtype=torch.float64, device=dev)
+    loss_px = torch.empty(B, HW, dtype=torch.float32, device=dev)
+    _check(L.sea_train_ce_fwd(_p(logits), DTYPE_CODE[logits.dtype], _p(y), _p(weight), int(ignore_label), float(thresh),
+                              0 if ohem else 1, B, Cc, HW, _p(loss_px), _p(workspace), nb, _p(words), _stream()),
+           "sea_train_ce_fwd")
+    if ohem:
+        _check(L.sea_train_ohem_select(_p(loss_px), B * HW, _p(workspace), nb, _p(words), _stream()),
+               "sea_train_ohem_select")
+    return words.view(torch.float32)[TRAIN_WORDS_F32["loss"]].clone(), loss_px, words
+
+
+def train_ce_backward(logits, y, weight, ignore_label: int, ohem: bool, loss_px, words, g):
+    """T2 backward: d loss / d logits in the logits' dtype.  ``g``: the upstream gradient, a 0-dim device tensor."""
+    B, Cc, HW, weight = _train_args(logits, y, weight)
+    _dev(loss_px, words, g)
+    if g.numel() != 1:
+        raise SeaNativeError("the upstream gradient of the criterion is a scalar")
+    g = g.reshape(1).to(torch.float32)
+    dlogits = torch.empty_like(logits)
+    _check(lib().sea_train_ce_bwd(_p(logits), DTYPE_CODE[logits.dtype], _p(y), _p(weight), int(ignore_label),
+                                  1 if ohem else 0, B, Cc, HW, _p(_f32c(loss_px)), _p(g), _p(words), _p(dlogits),
+                                  _stream()), "sea_train_ce_bwd")
+    return dlogits
 
 
 # ------------------------------------------------------------------------------------------------ K3

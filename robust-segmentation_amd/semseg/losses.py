@@ -1,5 +1,12 @@
-"""Training-time losses (counterpart of semseg/losses.py:6-109): plain PyTorch modules used by the
-PIR-AT OUTER step; not on the attack hot path, kept for ``get_loss`` API parity."""
+"""Training-time losses (counterpart of semseg/losses.py:6-109) of the PIR-AT OUTER step.
+
+``CrossEntropy`` and ``OhemCrossEntropy`` take ``native=True`` to run on the device through T2 (csrc/train_loss.hip:
+fused forward, hard-pixel selection and backward, no host read, no log-softmax kept for the backward).  The default
+``native=False`` is the plain PyTorch arithmetic every existing caller gets.  With ``native=True`` a tensor that is not
+on the HIP device raises ``SeaNativeError`` (no CPU fallback), and so do logits that are neither dense NCHW nor
+channels_last; channels_last logits, for which T2 has no kernel, go through the PyTorch criterion (with its host
+synchronisations for OHEM).  The native loss is an fp32 scalar whatever the logits' dtype.  ``Dice`` stays PyTorch: it takes probabilities, and no configuration of the reference
+uses it."""
 from __future__ import annotations
 
 import torch
@@ -7,6 +14,41 @@ from torch import Tensor, nn
 from torch.nn import functional as F
 
 __all__ = ["CrossEntropy", "OhemCrossEntropy", "Dice"]
+
+
+class _NativeCriterion(torch.autograd.Function):
+    """T2: forward (+ OHEM select) and backward of one prediction; the gradient is for ``preds`` only."""
+
+    @staticmethod
+    def forward(ctx, preds, labels, weight, ignore_label, thresh, ohem):
+        from . import _native as N
+        loss, loss_px, words = N.train_ce_forward(preds, labels, weight, ignore_label, thresh, ohem)
+        ctx.save_for_backward(preds, labels, loss_px, words)
+        ctx.weight, ctx.ignore_label, ctx.ohem = weight, ignore_label, ohem
+        ctx.mark_non_differentiable(words)
+        return loss, words   # fp32 whatever the logits' dtype (what autocast makes of F.cross_entropy)
+
+    @staticmethod
+    def backward(ctx, g, _g_words):
+        from . import _native as N
+        preds, labels, loss_px, words = ctx.saved_tensors
+        return (N.train_ce_backward(preds, labels, ctx.weight, ctx.ignore_label, ctx.ohem, loss_px, words, g),
+                None, None, None, None, None)
+
+
+def _native_forward(module, preds, labels, thresh, ohem):
+    from . import _native as N
+    if not (preds.is_cuda and labels.is_cuda):
+        raise N.SeaNativeError("native=True criteria work on HIP device tensors only (no CPU fallback)")
+    if not preds.is_contiguous():
+        if preds.dim() == 4 and preds.is_contiguous(memory_format=torch.channels_last):
+            return None            # channels_last: no T2 kernel for that layout, the torch criterion runs (module docstring)
+        raise N.SeaNativeError("native=True criteria take dense NCHW (or channels_last) logits; got strides "
+                               f"{tuple(preds.stride())} for shape {tuple(preds.shape)}: call .contiguous() first")
+    w = module.criterion.weight
+    loss, module.last_words = _NativeCriterion.apply(preds, labels, None if w is None else w.detach().float(),
+                                                     module.criterion.ignore_index, thresh, ohem)
+    return loss
 
 
 class _AuxWeighted(nn.Module):
@@ -22,24 +64,38 @@ class _AuxWeighted(nn.Module):
 
 
 class CrossEntropy(_AuxWeighted):
-    def __init__(self, ignore_label: int = 255, weight: Tensor = None, aux_weights=(1, 0.4, 0.4)) -> None:
+    def __init__(self, ignore_label: int = 255, weight: Tensor = None, aux_weights=(1, 0.4, 0.4),
+                 native: bool = False) -> None:
         super().__init__()
         self.aux_weights = list(aux_weights)
+        self.native = native
+        self.last_words = None      # native: the device words of the last prediction (debugging / tests)
         self.criterion = nn.CrossEntropyLoss(weight=weight, ignore_index=ignore_label)
 
     def _forward(self, preds, labels):
+        if self.native:
+            loss = _native_forward(self, preds, labels, 0.0, False)
+            if loss is not None:
+                return loss
         return self.criterion(preds, labels)
 
 
 class OhemCrossEntropy(_AuxWeighted):
-    def __init__(self, ignore_label: int = 255, weight: Tensor = None, thresh: float = 0.7, aux_weights=(1, 1)) -> None:
+    def __init__(self, ignore_label: int = 255, weight: Tensor = None, thresh: float = 0.7, aux_weights=(1, 1),
+                 native: bool = False) -> None:
         super().__init__()
         self.ignore_label = ignore_label
         self.aux_weights = list(aux_weights)
+        self.native = native
+        self.last_words = None
         self.thresh = -torch.log(torch.tensor(thresh, dtype=torch.float))
         self.criterion = nn.CrossEntropyLoss(weight=weight, ignore_index=ignore_label, reduction="none")
 
     def _forward(self, preds, labels):
+        if self.native:
+            loss = _native_forward(self, preds, labels, float(self.thresh), True)
+            if loss is not None:
+                return loss
         n_min = labels[labels != self.ignore_label].numel() // 16
         loss = self.criterion(preds, labels).view(-1)
         hard = loss[loss > self.thresh]
@@ -64,8 +120,10 @@ class Dice(_AuxWeighted):
         return (torch.sum(1 - score, dim=-1) / k).mean()
 
 
-def get_loss(loss_fn_name: str = "CrossEntropy", ignore_label: int = 255, cls_weights: Tensor = None):
+def get_loss(loss_fn_name: str = "CrossEntropy", ignore_label: int = 255, cls_weights: Tensor = None,
+             native: bool = False):
     assert loss_fn_name in __all__, f"Unavailable loss function name >> {loss_fn_name}.\nAvailable loss functions: {__all__}"
     if loss_fn_name == "Dice":
         return Dice()
-    return {"CrossEntropy": CrossEntropy, "OhemCrossEntropy": OhemCrossEntropy}[loss_fn_name](ignore_label, cls_weights)
+    return {"CrossEntropy": CrossEntropy, "OhemCrossEntropy": OhemCrossEntropy}[loss_fn_name](ignore_label, cls_weights,
+                                                                                        native=native)

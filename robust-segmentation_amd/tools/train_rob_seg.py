@@ -114,6 +114,16 @@ def build_attack(train_cfg):
     return apgd
 
 
+def build_criterion(cfg, native: bool):
+    """--native-criterion: the Segmenter branch's criterion from the config's LOSS.NAME on T2 (csrc/train_loss.hip), with
+    the branch's ignore label -1 and no class weights; None without the flag (F.cross_entropy, as before).  The native
+    criterion returns its value in fp32 whatever the logits' dtype, as F.cross_entropy does under autocast."""
+    if not native:
+        return None
+    from semseg.losses import get_loss
+    return get_loss(cfg.get("LOSS", {}).get("NAME", "CrossEntropy"), -1, None, native=True)
+
+
 def _main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--cfg", type=str, default="configs/ade20k_convnext.yaml")
@@ -132,6 +142,9 @@ def _main(argv=None):
                          "all-reduce computes); used to check the multi-rank run")
     ap.add_argument("--dump_params", type=str, default=None,
                     help="save a sample of parameter tensors and of their (rank-averaged) gradients of the last step")
+    ap.add_argument("--native-criterion", action="store_true",
+                    help="Segmenter branch: compute the outer step's criterion with get_loss(cfg LOSS.NAME, -1, None, "
+                         "native=True) (T2, csrc/train_loss.hip) instead of F.cross_entropy")
     args = ap.parse_args(argv)
     with open(args.cfg) as f:
         cfg = yaml.load(f, Loader=yaml.SafeLoader)
@@ -194,6 +207,9 @@ def _main(argv=None):
             cfg["SCHEDULER"]["WARMUP_RATIO"]))
     amp = bool(train_cfg["AMP"]) or args.bf16
     attack_fn = build_attack(train_cfg) if train_cfg["ADVERSARIAL"] else None
+    criterion = build_criterion(cfg, args.native_criterion)
+    if criterion is not None:
+        criterion = criterion.to(dev)
 
     def one_step(i):
         idx = [(i * bs + j) % n for j in range(bs)]
@@ -222,6 +238,8 @@ def _main(argv=None):
                     loss = main_loss + 0.4 * aux_loss
                 elif model_cfg["NAME"] == "UperNetForSemanticSegmentation":
                     loss, _ = ddp(img, lbl)
+                elif criterion is not None:
+                    loss = criterion(ddp(img).contiguous(), lbl)
                 else:
                     loss = torch.nn.functional.cross_entropy(ddp(img), lbl, ignore_index=-1)
             # DDP all-reduces (averages) the gradient buckets in backward: the step's only collective.  Emulated
