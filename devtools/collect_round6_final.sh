@@ -35,7 +35,6 @@ b() { python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-model-rooflin
     echo "  SEA_FUSE_CLS_GATE=0    (separate gate pass)   $(SEA_FUSE_CLS_GATE=0 b)"
     echo "  SEA_WINO_IN_VEC4=0     (2 channels per lane)  $(SEA_WINO_IN_VEC4=0 b)"
     echo "  SEA_TAP_INNER=0        (general tap weights)  $(SEA_TAP_INNER=0 b)"
-    echo "  SEA_GEMM_BIG_WAVES=4   (4 x 128x128 waves)    $(SEA_GEMM_BIG_WAVES=4 b)"
   done
   echo "# UperNet-ConvNeXt-S C=151 / Segmenter ViT-S C=151: K2u (fused final up-sampling + loss) on (shipped for C >= 96) vs off"
   echo "  cnxs shipped $(b --backbone ConvNeXt-S_CVST --classes 151)   --no-fuse-upsample $(b --backbone ConvNeXt-S_CVST --classes 151 --no-fuse-upsample)"

@@ -41,9 +41,8 @@ def main():
         wt = torch.randn(49, Cc, device="cuda") * 0.1
         bb = torch.randn(Cc, device="cuda")
         for name, bias, fl in (("fwd", bb, 0), ("bwd-data", None, 1)):
-            def run(x, ab):      # A/B switches travel through the environment (SEA_DWCONV_AB, read per call here)
-                os.environ["SEA_DWCONV_AB"] = str(ab)
-                return N.dwconv7x7_nhwc(x, wt, bias, flip=bool(fl))
+            def run(x, ab):      # the launcher's A/B mask, per call
+                return N.dwconv7x7_nhwc(x, wt, bias, flip=bool(fl), ab=ab)
             ya = run(xs[0], 0)
             same = torch.equal(ya, run(xs[0], 2))
             mb = 8 * xs[0].numel() / 1e6

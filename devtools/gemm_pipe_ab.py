@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""M8 A/B on one lease: the single-stage K loop (sea_gemm_split_pipeline(0)) against the ping-pong pipeline (1) on the
+"""M8 A/B on one lease: the single-stage K loop (N.gemm_split(..., pipe=0)) against the ping-pong pipeline (pipe=1) on the
 frozen-weight GEMM shapes of one APGD step (UperNet-ConvNeXt-T, B = 8, 512 x 512), alternating, 3 rounds of `reps` launches
 each, bitwise comparison of the outputs.      python devtools/gemm_pipe_ab.py [terms ...]"""
 import os
@@ -61,8 +61,7 @@ def main():
             ts = {0: [], 1: [], 3: []}
             for rnd in range(3):
                 for pipe in pipes:
-                    L.sea_gemm_split_pipeline(pipe)
-                    ts[pipe].append(timed(lambda: N.gemm_split(A, Wp, out=outs[min(pipe, 2)], **kw), reps))
+                    ts[pipe].append(timed(lambda: N.gemm_split(A, Wp, out=outs[min(pipe, 2)], pipe=pipe, **kw), reps))
             same = torch.equal(outs[0], outs[1]) and (3 not in pipes or torch.equal(outs[0], outs[2]))
             prod = 3 if terms in (22, 2) else 1
             t0, t1 = min(ts[0]), min(ts[1])
@@ -75,7 +74,6 @@ def main():
                   f"bits {'EQUAL' if same else 'DIFFER'}", flush=True)
             del outs
         del A, W
-    L.sea_gemm_split_pipeline(1)
     for terms in terms_list:
         print(f"sum over shapes, terms {terms}: single-stage {tot[terms, 0] / 1e3:.2f} ms   ping-pong {tot[terms, 1] / 1e3:.2f} ms")
 

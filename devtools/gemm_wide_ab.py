@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B of the 128 x 384 one-block-per-CU kernel (sea_gemm_split_pipeline(3)) against the 128 x 128 kernels (0 = single-stage,
+"""A/B of the 128 x 384 one-block-per-CU kernel (N.gemm_split(..., pipe=3)) against the 128 x 128 kernels (pipe 0 = single-stage,
 1 = ping-pong) on the products of the 32 x 32- and 64 x 64-pixel ConvNeXt stages, with their prologues and split-K, bitwise
 comparison.      python devtools/gemm_wide_ab.py"""
 import os
@@ -34,7 +34,6 @@ def timed(fn, reps=30):
     return e0.elapsed_time(e1) / reps * 1e3
 
 
-L = N.lib()
 for name, M, K, Nn, kw in CASES:
     A = torch.randn(M, K, device="cuda")
     W = torch.randn(Nn, K, device="cuda") / K ** 0.5
@@ -48,12 +47,10 @@ for name, M, K, Nn, kw in CASES:
     outs, ts = {}, {}
     for rnd in range(2):
         for pipe in (0, 1, 3):
-            L.sea_gemm_split_pipeline(pipe)
             outs[pipe] = torch.empty(M, Nn, device="cuda")
-            tt = timed(lambda: N.gemm_split(A, Wp, out=outs[pipe], **kwargs))
+            tt = timed(lambda: N.gemm_split(A, Wp, out=outs[pipe], pipe=pipe, **kwargs))
             ts[pipe] = min(ts.get(pipe, 1e9), tt)
     same = torch.equal(outs[0], outs[3]) and torch.equal(outs[0], outs[1])
     flop = 2.0 * M * K * Nn * 3
     print(f"{name:52s} M={M:6d} K={K:4d} N={Nn:4d}  single-stage {ts[0]:6.1f} us  ping-pong {ts[1]:6.1f} us  one-block-per-CU {ts[3]:6.1f} us "
           f"({flop / ts[3] / 1e6:5.0f} TF/s)  x{ts[0] / ts[3]:.2f}  bits {'EQUAL' if same else 'DIFFER'}", flush=True)
-L.sea_gemm_split_pipeline(2)

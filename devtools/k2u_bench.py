@@ -33,7 +33,8 @@ def timeit(fns, rounds=7, reps=5):
     return {k: (min(v), sorted(v)[len(v) // 2]) for k, v in best.items()}
 
 
-print("K2u kernel:", "general gather (SEA_K2U_POW2=0)" if os.environ.get("SEA_K2U_POW2") == "0" else "power-of-two, lanes = classes")
+POW2 = os.environ.get("SEA_K2U_POW2") != "0"
+print("K2u kernel:", "power-of-two, lanes = classes" if POW2 else "general gather (SEA_K2U_POW2=0)")
 for C, hl, lab in ((21, 128, "UperNet x4"), (151, 128, "UperNet x4"), (151, 32, "Segmenter x16")):
     g = torch.Generator(device="cuda").manual_seed(C + hl)
     low = torch.randn(B, C, hl, hl, generator=g, device="cuda") * 3
@@ -48,7 +49,7 @@ for C, hl, lab in ((21, 128, "UperNet x4"), (151, 128, "UperNet x4"), (151, 32, 
     pred8 = torch.empty(B, H, W, dtype=torch.uint8, device="cuda")
     dl = torch.empty(B, C, H, W, device="cuda")
     ws = N.loss_workspace(B, HW, "cuda")
-    wsu = torch.empty(N.lib().sea_loss_upsampled_workspace_bytes(B, C, hl, hl, H, W), dtype=torch.uint8, device="cuda")
+    wsu = torch.empty(N.lib().sea_loss_upsampled_workspace_bytes(B, C, hl, hl, H, W, int(POW2)), dtype=torch.uint8, device="cuda")
 
     def unfused(mode=1):
         up = M._UpsampleBilinear.apply(low.detach().requires_grad_(True), (H, W)) if hasattr(M, "_UpsampleBilinear") else None
@@ -56,9 +57,9 @@ for C, hl, lab in ((21, 128, "UperNet x4"), (151, 128, "UperNet x4"), (151, 32, 
         return torch.autograd.grad(up, up.grad_fn.next_functions[0][0].variable, r["dlogits"])
 
     t = timeit({
-        f"K2u C={C} {lab} mask-ce-bal +grad": lambda: N.loss_fwd_bwd_upsampled(low, y8, w, 1, 3, 1.0 / HW, True, pred=pred8, dlow=dlow, workspace=wsu),
-        f"K2u C={C} {lab} js +grad": lambda: N.loss_fwd_bwd_upsampled(low, y8, w, 2, 3, 1.0 / HW, True, pred=pred8, dlow=dlow, workspace=wsu),
-        f"K2u C={C} {lab} no-grad": lambda: N.loss_fwd_bwd_upsampled(low, y8, w, 1, 3, 1.0 / HW, False, pred=pred8, workspace=wsu),
+        f"K2u C={C} {lab} mask-ce-bal +grad": lambda: N.loss_fwd_bwd_upsampled(low, y8, w, 1, 3, 1.0 / HW, True, pred=pred8, dlow=dlow, workspace=wsu, pow2=POW2),
+        f"K2u C={C} {lab} js +grad": lambda: N.loss_fwd_bwd_upsampled(low, y8, w, 2, 3, 1.0 / HW, True, pred=pred8, dlow=dlow, workspace=wsu, pow2=POW2),
+        f"K2u C={C} {lab} no-grad": lambda: N.loss_fwd_bwd_upsampled(low, y8, w, 1, 3, 1.0 / HW, False, pred=pred8, workspace=wsu, pow2=POW2),
         f"M2 up-sample + K2 + M2 backward C={C} {lab}": unfused,
     })
     for k, (mn, med) in t.items():

@@ -10,8 +10,10 @@
  *
  * Conventions
  *   - plain pointers + sizes, no torch types; all device pointers are HBM addresses on the
- *     current HIP device; the caller allocates and owns every buffer; the library keeps no global
+ *     current HIP device; the caller allocates and owns every buffer; the library keeps no mutable
  *     state and never allocates, frees or synchronises -> re-entrant per stream, graph-capturable.
+ *     Which kernel runs is a function of the call's arguments alone (plus the two read-only words of
+ *     sea_process_config); defaults and environment variables are the caller's business.
  *   - `stream` is a hipStream_t passed as void* (NULL = the legacy default stream).  All device
  *     work is stream ordered and asynchronous.
  *   - return value: 0 on success, otherwise a hipError_t value (1 = invalid argument).  Nothing
@@ -45,8 +47,15 @@ extern "C" {
 #define SEA_LAYOUT_NHWC 1
 
 /* library / build identification */
-int sea_abi_version(void);
+int sea_abi_version(void);   /* 2: kernel variants are arguments (sea_gemm_split*, sea_dwconv7x7_nhwc*, ...), no setters */
 const char* sea_build_info(void);
+/* The process configuration: two A/B switches that dozens of launchers consult, read from the environment ONCE at first use
+ * and immutable afterwards; every other choice is an argument of the call it concerns.  Read-only; -1 for an unknown word.
+ *   SEA_CONFIG_XCD_ORDER         env SEA_XCD_ORDER = 0 | 1 | 2: XCD-aware block order off / on (default) / also for pure streams
+ *   SEA_CONFIG_UPSAMPLE_GENERAL  env SEA_UPSAMPLE_GENERAL = 1: general-ratio bilinear kernels even for power-of-two factors */
+#define SEA_CONFIG_XCD_ORDER 0
+#define SEA_CONFIG_UPSAMPLE_GENERAL 1
+int sea_process_config(int which);
 /* host only: the multiplier / shift the kernels use to divide a work index (< 2^31) by d without an integer division:
  * n / d == (mulhi32(n, *m) + n) >> *s.  Exposed for the unit test of that arithmetic. */
 int sea_fastdiv_magic(uint32_t d, uint32_t* m, uint32_t* s);
@@ -133,13 +142,15 @@ int sea_loss_fwd_bwd_tuned(const void* logits, int dtype, int layout, const void
  *   loss_sum / track_sum / n_correct as in K2 (sums over the H*W full-resolution pixels)
  * Any scale H/h, W/w >= 1 (ATen's align_corners=False source-index rule).  Gradients are gathered in a
  * fixed order (no atomics): deterministic.
+ * pow2 != 0 (shipped): factors 4 and 16 take the kernel with lanes along the classes; pow2 = 0 keeps the general gather
+ * kernel for every factor (A/B).  Pass the same value to both calls: it sizes the workspace.
  */
-size_t sea_loss_upsampled_workspace_bytes(int B, int C, int h, int w, int H, int W);
+size_t sea_loss_upsampled_workspace_bytes(int B, int C, int h, int w, int H, int W, int pow2);
 int sea_loss_fwd_bwd_upsampled(const float* low, const void* y, int y_bytes, const float* w, int mode,
                                int track_mode, int B, int C, int h, int wl, int H, int W, float grad_scale,
                                float* dlow, void* pred, int pred_bytes, void* workspace,
                                size_t workspace_bytes, float* loss_sum, float* track_sum,
-                               int32_t* n_correct, void* stream);
+                               int32_t* n_correct, int pow2, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * K3  per-class integer statistics.
@@ -242,14 +253,17 @@ int sea_worst_miou_greedy(const float* ints, const float* unions, int A, int N, 
 int sea_dwconv7x7(const float* x, const float* w, const float* bias, float* y, int B, int C, int H,
                   int W, int flip, void* stream);
 /* channels_last variant: x, y (B,H,W,C) contiguous, wt (49,C) taps-major (= w.view(C,49).T), C % 4 == 0.
- * With it the whole ConvNeXt block runs in NHWC: no permute / layout copy is left. */
+ * With it the whole ConvNeXt block runs in NHWC: no permute / layout copy is left.
+ * ab: A/B switches of the launcher, 0 = the shipped dispatch; a mask of 2 (plain block order), 4 (one output row per lane),
+ * 8 (two rows per lane), 16 (the kernels without the software pipeline), 32 / 64 (filter rows from LDS never / always).
+ * Every combination gives the same bits. */
 int sea_dwconv7x7_nhwc(const float* x, const float* wt, const float* bias, float* y, int B, int C,
-                       int H, int W, int flip, void* stream);
+                       int H, int W, int flip, unsigned ab, void* stream);
 /* same, plus an optional addend of y's shape: y = conv(x) + addend (added after the taps: bitwise what a separate
  * element-wise add gives).  The backward of a ConvNeXt block (x + branch(x), convnext_orig.py:75-86) passes the skip
  * gradient here, which removes one element-wise pass per block.  bias and addend are mutually exclusive. */
 int sea_dwconv7x7_nhwc_add(const float* x, const float* wt, const float* bias, const float* addend, float* y, int B,
-                           int C, int H, int W, int flip, void* stream);
+                           int C, int H, int W, int flip, unsigned ab, void* stream);
 
 /* M2  (model side) bilinear up-sampling, align_corners=False, fp32 NCHW planes: forward and its
  * backward w.r.t. the input (gather formulation, deterministic; ATen scatters with atomics).
@@ -291,18 +305,21 @@ int sea_upsample_bilinear_nhwc_bwd(const float* gy, float* gx, int B, int C, int
  *   sea_wino_output_transform:  M (A*A, T, C) -> y (B,H,W,C) = act(scale[c] * (conv + addend) + bias[c]);
  *                               addend (B,H,W,C) / scale / bias may be NULL, act = ReLU when relu != 0.  With scale/bias = the folded
  *                               eval-mode BatchNorm this is the whole ConvModule (uperforseg.py:119-146).
- * C % 4 == 0, 16-byte aligned pointers. */
+ * C % 4 == 0, 16-byte aligned pointers.
+ * vec4 (m = 4; A/B): four channels per lane instead of two; shipped: 1 in the input transforms, 0 in the output
+ * transform. */
 int64_t sea_wino_tiles(int B, int H, int W, int m);
 int sea_wino_input_transform(const float* x, int64_t x_pixel_stride, const float* gate, const float* scale,
-                             float* V, int64_t v_tile_stride, int B, int C, int H, int W, int m, void* stream);
+                             float* V, int64_t v_tile_stride, int B, int C, int H, int W, int m, int vec4, void* stream);
 int sea_wino_filter_transform(const float* w, float* U, int Cout, int Cin, int m, int flip, void* stream);
 /* sea_wino_input_transform that also max-accumulates, per tile t, the float bits of max|V[.][t][.]| into amax_out[t]
  * (sea_wino_tiles pre-zeroed words): the per-row fp16 x 2 scales of the Winograd-domain GEMMs (sea_gemm_split_f16 with
  * amax_rows = 1), each depending on its own tile only.  T < 2^31. */
 int sea_wino_input_transform_amax(const float* x, int64_t x_pixel_stride, const float* gate, const float* scale, float* V,
-                                  int64_t v_tile_stride, int B, int C, int H, int W, int m, uint32_t* amax_out, void* stream);
+                                  int64_t v_tile_stride, int B, int C, int H, int W, int m, int vec4, uint32_t* amax_out,
+                                  void* stream);
 int sea_wino_output_transform(const float* M, const float* addend, const float* scale, const float* bias,
-                              int relu, float* y, int B, int C, int H, int W, int m, void* stream);
+                              int relu, float* y, int B, int C, int H, int W, int m, int vec4, void* stream);
 
 /* M5  (model side) LayerNorm over the last dimension of a (rows, C) fp32 tensor with few channels (ConvNeXt:
  * C = 48..768, eps 1e-6; convnext_orig.py:19-40), forward and input gradient (w, b frozen).  A row is owned
@@ -352,9 +369,11 @@ int sea_ln_gelu_cl_bwd(const float* da, int a_nchw, const float* y, const float*
  *   sea_tap_gather_fwd: extra (B,H,W,C) (+)= sum_taps shift_tap(up(G[..., tap, :]))   (accumulate != 0: +=)
  *   sea_tap_gather_bwd: gz (B,H,W,C) -> dG (B,h,w,9,C), the exact adjoint (then df = dG @ W^T)
  *   sea_gate_scale    : out = gate > 0 ? g * scale[c] : 0, the backward of relu(scale * z + shift) (NHWC)
- * `extra` enters sea_wino_output_transform as `addend`.  C % 4 == 0, 16-byte aligned. */
+ * `extra` enters sea_wino_output_transform as `addend`.  C % 4 == 0, 16-byte aligned.
+ * inner (forward): non-zero = interior blocks take the path with compile-time interpolation weights (shipped), 0 = run-time
+ * weights everywhere (A/B). */
 int sea_tap_gather_fwd(const float* G, float* extra, int accumulate, int B, int C, int h, int w, int H, int W,
-                       void* stream);
+                       int inner, void* stream);
 int sea_tap_gather_bwd(const float* gz, float* dG, int B, int C, int h, int w, int H, int W, void* stream);
 int sea_gate_scale(const float* g, const float* gate, const float* scale, float* out, int64_t pixels, int C,
                    void* stream);
@@ -381,21 +400,14 @@ int sea_patch2x2(const float* src, float* dst, int B, int H, int W, int C, int i
  * q, k, v: element (b, h, t, d) at ptr + b*sb + h*sh + t*st + d floats (d contiguous; the three may be slices of one
  *   packed (B,T,3,H,64) qkv tensor: sb = T*3*H*64, sh = 64, st = 3*H*64).  D must be 64.  Rows 16-byte aligned.
  * out (B,T,H*64) contiguous: the layout the output projection consumes.  lse (B,H,T): log-sum-exp of the scaled scores.
- * sea_attention_bwd: grad_out (B,T,H*64) contiguous; delta (B,H,T) scratch; dq/dk/dv are written with strides
+ * backward: grad_out (B,T,H*64) contiguous; delta (B,H,T) scratch; dq/dk/dv are written with strides
  *   (gsb, gsh, gst) -- pass slices of one (B,T,3,H,64) gradient tensor to get d(qkv) without a concatenation.
  *   Deterministic (no atomics): S is recomputed in the dq kernel and in the dk/dv kernel.
- * Arithmetic (round 3, csrc/attention_bf16.hip): by default the products run on v_mfma_f32_32x32x16_bf16 with every fp32
- *   operand split into bf16 terms, fp32 accumulate: three terms (= the fp32 operands exactly, six products) in the
- *   forward, two terms in the backward (the attack consumes only the sign of the input gradient).  Environment, read per
- *   call: SEA_ATTN_TERMS / SEA_ATTN_TERMS_BWD = 3 | 2 | 0 (0 = the fp32 MFMA kernels of csrc/attention.hip).
+ * Arithmetic (csrc/attention_bf16.hip): the products run on v_mfma_f32_32x32x16_bf16 with every fp32 operand split into
+ *   `terms` bf16 numbers, fp32 accumulate: 3 (= the fp32 operands exactly, six products) or 2; terms = 0 selects the fp32 MFMA
+ *   kernels of csrc/attention.hip.  The caller chooses per call; the library reads no environment.
  */
-int sea_attention_fwd(const float* q, const float* k, const float* v, int64_t sb, int64_t sh, int64_t st, int B, int H,
-                      int T, int D, float scale, float* out, float* lse, void* stream);
-int sea_attention_bwd(const float* q, const float* k, const float* v, int64_t sb, int64_t sh, int64_t st, int B, int H,
-                      int T, int D, float scale, const float* out, const float* grad_out, const float* lse,
-                      float* delta, float* dq, float* dk, float* dv, int64_t gsb, int64_t gsh, int64_t gst,
-                      void* stream);
-/* sea_attention_bwd with the number of bf16 terms of the backward products given by the caller (3, 2, or 0 = fp32 MFMA):
+/* the backward, with the number of bf16 terms of its products given by the caller (3, 2, or 0 = fp32 MFMA):
  * 3 when the weights are trained through this backward, 2 when only the sign of the input gradient is consumed. */
 int sea_attention_bwd_terms(const float* q, const float* k, const float* v, int64_t sb, int64_t sh, int64_t st, int B, int H,
                             int T, int D, float scale, const float* out, const float* grad_out, const float* lse,
@@ -405,7 +417,7 @@ int sea_attention_bwd_terms(const float* q, const float* k, const float* v, int6
  * three-term bf16 mode at the cost of the two-term one).  Power-of-two scales: the exact row maximum for a lane's own
  * Q / K / V / dO row, one per (image, head) for the staged tiles (from a pre-pass this call launches), analytic bounds for the
  * soft-max operands P and dS.  amax_ws: 4 B H uint32 words of device scratch. */
-/* sea_attention_fwd with the number of bf16 terms of the products given by the caller (3, 2, or 0 = fp32 MFMA) */
+/* the forward, with the number of bf16 terms of the products given by the caller (3, 2, or 0 = fp32 MFMA) */
 int sea_attention_fwd_terms(const float* q, const float* k, const float* v, int64_t sb, int64_t sh, int64_t st, int B, int H,
                             int T, int D, float scale, float* out, float* lse, int terms, void* stream);
 int sea_attention_fwd_f16(const float* q, const float* k, const float* v, int64_t sb, int64_t sh, int64_t st, int B, int H,
@@ -433,13 +445,26 @@ int sea_attention_bwd_f16(const float* q, const float* k, const float* v, int64_
  *   output row and the activations are scaled by a power of two derived from max|A|, which the caller obtains on the device
  *   with sea_absmax_bits (one 4-byte word, no host round trip) and hands to sea_gemm_split_f16; the epilogue undoes both
  *   scales exactly.  Elements more than 2^28 below the tensor's maximum flush to zero.
+ *
+ * variant (sea_gemm_split, _f16, _fused): which of the kernels behind the entry runs, per call.  0 = the shipped dispatch
+ *   (chosen per launch from the shape, 32x32x16 fragments).  SEA_GEMM_PIPE_SINGLE = the single-stage K loop (three blocks per
+ *   CU), SEA_GEMM_PIPE_PINGPONG = two LDS stages, one barrier per K step, the operand split in the shadow of the wave's own
+ *   MFMAs (two blocks per CU), SEA_GEMM_PIPE_BIG = the one-block-per-CU 256 x 256 / 128 x 384 kernels wherever they apply.
+ *   Same split and same MFMA order: every pipeline gives the same bits.  | SEA_GEMM_SHAPE16 = v_mfma_f32_16x16x32_* fragments
+ *   (single-stage loop only; last bits differ: summation order).  Any other bit -> invalid argument.
  */
+#define SEA_GEMM_VARIANT_DEFAULT 0u
+#define SEA_GEMM_PIPE_SINGLE 1u
+#define SEA_GEMM_PIPE_PINGPONG 2u
+#define SEA_GEMM_PIPE_BIG 3u
+#define SEA_GEMM_PIPE_MASK 3u
+#define SEA_GEMM_SHAPE16 4u
 int64_t sea_gemm_split_packed_bytes(int N, int K, int terms);
 int sea_absmax_bits(const float* A, int64_t lda, int M, int K, int batch, int64_t strideA, int rows_per_word,
                     uint32_t* out_bits, void* stream);
 int sea_gemm_split_f16(const float* A, int64_t lda, const void* Wp, float* C, int64_t ldc, const float* bias, int relu, int M,
                        int N, int K, int batch, int64_t strideA, int64_t strideW_bytes, int64_t strideC,
-                       const uint32_t* amax_bits, int amax_rows, uint32_t* out_amax, void* stream);
+                       const uint32_t* amax_bits, int amax_rows, uint32_t* out_amax, unsigned variant, void* stream);
 /* The activation scale is a power of two PER ROW of A, taken from amax_bits[row / amax_rows] (amax_rows = 0: one word for
  * the whole tensor): a word is the float bits of any upper bound of max|A| over its rows (all batch entries).  With one
  * word per image (amax_rows = rows of an image) or per row, an image's result does not depend on the images it shares a
@@ -487,10 +512,10 @@ typedef struct SeaGemmEpilogue {
 int sea_gemm_split_fused(const float* A, int64_t lda, const void* Wp, float* C, int64_t ldc, const float* bias, int relu, int M,
                          int N, int K, int terms, int batch, int64_t strideA, int64_t strideW_bytes, int64_t strideC,
                          const uint32_t* amax_bits, int amax_rows, uint32_t* out_amax, const SeaGemmEpilogue* epi,
-                         void* stream);
+                         unsigned variant, void* stream);
 int sea_gemm_split(const float* A, int64_t lda, const void* Wp, float* C, int64_t ldc, const float* bias, int relu, int M,
                    int N, int K, int terms, int batch, int64_t strideA, int64_t strideW_bytes, int64_t strideC,
-                   void* stream);
+                   unsigned variant, void* stream);
 /* ------------------------------------------------------------------------------------------------
  * M10  the decode head's classifier, a 1 x 1 convolution onto a SMALL number of classes (semseg/models/uperforseg.py:262
  *      `cls_seg`; reference autograd for the input gradient), forward and input gradient for frozen weights, on
@@ -548,16 +573,6 @@ int sea_mlp_fused_fwd(const float* x, int64_t ldx, const void* W1p, const float*
 int sea_mlp_fused_bwd(const float* g, int64_t ldg, const float* x, int64_t ldx, const void* W1p, const float* b1,
                       const void* W2tp, const void* W1tp, float* dx, int64_t lddx, int M, int C, int H,
                       const uint32_t* amax_x, const float* amax_mul_dev, void* stream);
-/* Tuning knob of the sea_gemm_split* kernels: MFMA fragment shape, 32 (v_mfma_f32_32x32x16_{f16,bf16}; default) or 16
- * (v_mfma_f32_16x16x32_*; also env SEA_GEMM_SHAPE=16).  Any other argument only queries.  Returns the previous shape. */
-int sea_gemm_split_mfma_shape(int shape);
-/* K-loop pipeline of the sea_gemm_split* kernels at one or two terms per operand (32x32x16 fragments): 0 = the single-stage
- * loop (three blocks per CU), 1 = ping-pong (two LDS stages, one barrier per K step, the operand split in the shadow of the
- * wave's own MFMAs, loads two K steps ahead, two blocks per CU), 2 = chosen per launch (default; also env SEA_GEMM_PIPE=0|1|2):
- * ping-pong for launches with a prologue on A whose grid fills two blocks per CU.  Same split and same MFMA order: the kernels give the
- * same bits.  Any other argument only queries.  Returns the previous setting. */
-int sea_gemm_split_pipeline(int pipe);
-
 /* ------------------------------------------------------------------------------------------------
  * Measurement probes (bench.py / tools/kernel_bench.py only; nothing on the product path calls them).
  * sea_probe_stream_copy: dst[0:bytes] = src[0:bytes] with 16-byte-per-lane accesses (non_temporal != 0: nt loads and

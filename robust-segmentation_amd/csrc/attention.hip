@@ -377,15 +377,6 @@ extern "C" int sea_attention_fwd_f16(const float* q, const float* k, const float
   return sea_attention_fwd_f16x2(q, k, v, sb, sh, st, B, H, T, scale, amax_ws, out, lse, (hipStream_t)stream);
 }
 
-// SEA_ATTN_TERMS (forward) / SEA_ATTN_TERMS_BWD: 3 or 2 = bf16 terms per operand on v_mfma_f32_32x32x16_bf16, 0 = the fp32
-// MFMA kernels of this file.  Defaults: 3 (= the fp32 operands exactly) forward AND backward (round 4: the evaluation is
-// fp32-equivalent end to end; 2 backward was round 3's default: the attack consumes only the sign of the input gradient).
-static inline int attn_terms(bool backward) {   // looked up per call (two launches per layer): tests switch it in-process
-  const char* e = getenv(backward ? "SEA_ATTN_TERMS_BWD" : "SEA_ATTN_TERMS");
-  const int t = e ? atoi(e) : 3;
-  return (t == 2 || t == 3) ? t : 0;
-}
-
 static int attention_fwd_impl(const float* q, const float* k, const float* v, int64_t sb, int64_t sh, int64_t st, int B, int H,
                               int T, int D, float scale, float* out, float* lse, int terms, void* stream) {
   SEA_CHECK_ARG(q && k && v && out && lse && B > 0 && H > 0 && T > 0 && D == kD);
@@ -399,13 +390,8 @@ static int attention_fwd_impl(const float* q, const float* k, const float* v, in
   SEA_RETURN_LAST();
 }
 
-// q/k/v: element (b,h,t,d) at ptr + b*sb + h*sh + t*st + d (floats), d contiguous, head dim 64, 16-byte aligned rows.
-extern "C" int sea_attention_fwd(const float* q, const float* k, const float* v, int64_t sb, int64_t sh, int64_t st, int B, int H,
-                                 int T, int D, float scale, float* out, float* lse, void* stream) {
-  return attention_fwd_impl(q, k, v, sb, sh, st, B, H, T, D, scale, out, lse, attn_terms(false), stream);
-}
-
-// same, with the number of bf16 terms of the products chosen by the caller (3, 2, or 0 = fp32 MFMA kernels)
+// q/k/v: element (b,h,t,d) at ptr + b*sb + h*sh + t*st + d (floats), d contiguous, head dim 64, 16-byte aligned rows;
+// the number of bf16 terms of the products is chosen by the caller (3, 2, or 0 = fp32 MFMA kernels)
 extern "C" int sea_attention_fwd_terms(const float* q, const float* k, const float* v, int64_t sb, int64_t sh, int64_t st, int B,
                                        int H, int T, int D, float scale, float* out, float* lse, int terms, void* stream) {
   SEA_CHECK_ARG(terms == 0 || terms == 2 || terms == 3);
@@ -417,15 +403,7 @@ static int attention_bwd_impl(const float* q, const float* k, const float* v, in
                               float* delta, float* dq, float* dk, float* dv, int64_t gsb, int64_t gsh, int64_t gst,
                               int bwd_terms, void* stream, uint32_t* amax_ws = nullptr);
 
-extern "C" int sea_attention_bwd(const float* q, const float* k, const float* v, int64_t sb, int64_t sh, int64_t st, int B, int H,
-                                 int T, int D, float scale, const float* out, const float* grad_out, const float* lse,
-                                 float* delta, float* dq, float* dk, float* dv, int64_t gsb, int64_t gsh, int64_t gst,
-                                 void* stream) {
-  return attention_bwd_impl(q, k, v, sb, sh, st, B, H, T, D, scale, out, grad_out, lse, delta, dq, dk, dv, gsb, gsh, gst,
-                            attn_terms(true), stream);
-}
-
-// same, with the number of bf16 terms of the backward products chosen by the caller (3, 2, or 0 = fp32 MFMA kernels):
+// the number of bf16 terms of the backward products is chosen by the caller (3, 2, or 0 = fp32 MFMA kernels):
 // a caller that ALSO trains the weights through this backward wants 3; an attack that consumes sign(dx) takes 2
 extern "C" int sea_attention_bwd_terms(const float* q, const float* k, const float* v, int64_t sb, int64_t sh, int64_t st, int B,
                                        int H, int T, int D, float scale, const float* out, const float* grad_out,

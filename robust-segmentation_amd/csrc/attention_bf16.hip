@@ -849,7 +849,7 @@ __global__ __launch_bounds__(256, 2) void attn_dkv_f16_kernel(AttnPtrsB p, int T
 
 using namespace sea;
 
-// entry points used by csrc/attention.hip's sea_attention_fwd / sea_attention_bwd when the split path is selected
+// entry points used by the sea_attention_* entries of csrc/attention.hip when the split path is selected
 int sea_attention_fwd_bf16(const float* q, const float* k, const float* v, int64_t sb, int64_t sh, int64_t st, int B, int H, int T,
                            float scale, float* out, float* lse, int terms, hipStream_t stream) {
   AttnPtrsB p{q, k, v, sb, sh, st};

@@ -393,18 +393,12 @@ static void dw_pipe_launch(dim3 grid, hipStream_t s, const float4* x4, const flo
                      gx, HP, units, per_xcd);
 }
 
-// A/B switches of the NHWC depthwise launcher (development only; unset = shipped dispatch).  Looked up per call (one
-// getenv, ~0.1 us next to a 5 us launch) so that one process can compare variants.
-static inline int dwconv_ab_switches() {
-  const char* e = getenv("SEA_DWCONV_AB");
-  return e ? atoi(e) : 0;
-}
-
 // x, y: (B,H,W,C) contiguous fp32, C % 4 == 0, C <= 1024; wt: (49, C) taps-major; bias (C) or NULL; addend (same
 // shape as y) or NULL: y = conv(x) + addend, added after the taps (bitwise what a separate element-wise add gives; the
-// backward of a residual block hands the skip gradient in here).
+// backward of a residual block hands the skip gradient in here).  ab: A/B switches of the launcher (0 = shipped dispatch).
 extern "C" int sea_dwconv7x7_nhwc_add(const float* x, const float* wt, const float* bias, const float* addend, float* y,
-                                      int B, int C, int H, int W, int flip, void* stream) {
+                                      int B, int C, int H, int W, int flip, unsigned ab, void* stream) {
+  SEA_CHECK_ARG(ab < 128 && !(ab & 1));
   SEA_CHECK_ARG(x && wt && y && B > 0 && B <= 65535 && C > 0 && (C % 4) == 0 && C <= 1024 && H > 0 && H <= 65535 && W > 0);
   SEA_CHECK_ARG(((((uintptr_t)x) | ((uintptr_t)wt) | ((uintptr_t)y) | ((uintptr_t)bias) | ((uintptr_t)addend)) & 15) == 0);
   SEA_CHECK_ARG(!(addend && bias));  // forward: bias; backward-data: addend
@@ -415,13 +409,11 @@ extern "C" int sea_dwconv7x7_nhwc_add(const float* x, const float* wt, const flo
   hipStream_t s = (hipStream_t)stream;
   const float4 *x4 = (const float4*)x, *w4 = (const float4*)wt, *b4 = (const float4*)bias, *a4 = (const float4*)addend;
   float4* y4 = (float4*)y;
-  // `flip` is a boolean (any non-zero value = backward-data).  A/B switches for devtools/dwconv_bench.py come from the
-  // environment, read per call so that one process can compare variants: SEA_DWCONV_AB bit 1 (value 2): plain linear
-  // block order; bit 2 (value 4): one output row per lane; bit 3 (value 8): force two rows per lane.
+  // `flip` is a boolean (any non-zero value = backward-data).  A/B switches (devtools/dwconv_bench.py), the `ab` mask:
+  // bit 1 (value 2): plain linear block order; bit 2 (value 4): one output row per lane; bit 3 (value 8): force two rows per lane.
   // Two rows per lane pay off on the large maps (96 ch 128^2: 42 vs 44 us forward, 37 vs 42 us backward-data; 192 ch
   // 64^2: 21 vs 23 us) and lose on the small ones, where halving the number of blocks costs more than the loads saved
   // (768 ch 16^2: 11.2 vs 8.7 us); profiles/r2_dwconv_rows_ab.log.
-  const int ab = dwconv_ab_switches();
   const int CG0 = C / 4;
   const bool pipe_ok = !(ab & 16) && (CG0 == 24 || CG0 == 48 || CG0 == 96 || CG0 == 192) && (int64_t)B * H * W * C * 4 < (1ll << 31) &&
                        (W % DWN_STRIP) == 0;
@@ -442,7 +434,7 @@ extern "C" int sea_dwconv7x7_nhwc_add(const float* x, const float* wt, const flo
       hipLaunchKernelGGL((dwconv7x7_nhwc_kernel<F, BI, AD>), grid, block, 0, s, x4, w4, b4, a4, y4, CG, H, W, spb, gx,   \
                          units, per_xcd);                                                                               \
   } while (0)
-  // software-pipelined kernels for the ConvNeXt widths (bit 4, value 16, of SEA_DWCONV_AB: the plain kernels instead)
+  // software-pipelined kernels for the ConvNeXt widths (bit 4, value 16, of `ab`: the plain kernels instead)
   const bool piped = pipe_ok && (!two_rows || (H % 2) == 0);
 #define SEA_DW_PIPE(CGV, F, BI, AD)                                                              \
   do {                                                                                           \
@@ -452,7 +444,7 @@ extern "C" int sea_dwconv7x7_nhwc_add(const float* x, const float* wt, const flo
       dw_pipe_launch<CGV, 1, F, BI, AD>(grid, s, x4, w4, b4, a4, y4, H, W, gx, HP, units, per_xcd, wlds); \
   } while (0)
   // filter rows from LDS only for one row per lane (35 vs 40 us at 96 x 128^2; with two rows the copy costs what it saves:
-  // profiles/r6_dwconv_pipe_ab.log); bit 5 (value 32) of SEA_DWCONV_AB: never, bit 6 (value 64): always
+  // profiles/r6_dwconv_pipe_ab.log); bit 5 (value 32) of `ab`: never, bit 6 (value 64): always
   const bool wlds = !(ab & 32) && (!two_rows || (ab & 64));
 #define SEA_DW_PIPE_CG(F, BI, AD)                       \
   do {                                                  \
@@ -635,8 +627,8 @@ extern "C" int sea_dwconv7x7_nhwc_wgrad(const float* x, const float* gy, float* 
 }
 
 extern "C" int sea_dwconv7x7_nhwc(const float* x, const float* wt, const float* bias, float* y, int B, int C, int H,
-                                  int W, int flip, void* stream) {
-  return sea_dwconv7x7_nhwc_add(x, wt, bias, nullptr, y, B, C, H, W, flip, stream);
+                                  int W, int flip, unsigned ab, void* stream) {
+  return sea_dwconv7x7_nhwc_add(x, wt, bias, nullptr, y, B, C, H, W, flip, ab, stream);
 }
 
 // x, y: (planes = B*C, H, W) contiguous fp32; w: (C,1,7,7); bias: (C) or NULL.

@@ -345,8 +345,9 @@ __global__ __launch_bounds__(256) void gate_scale_kernel(const float4* __restric
 using namespace sea;
 
 // G (B,h,w,9,C) coarse per-tap maps -> extra (B,H,W,C) (+)= sum over the 3x3 taps of the shifted up-samplings
+// inner: 0 switches the compile-time-weight path of interior blocks off (A/B; the shipped value is 1)
 extern "C" int sea_tap_gather_fwd(const float* G, float* extra, int accumulate, int B, int C, int h, int w, int H, int W,
-                                  void* stream) {
+                                  int inner, void* stream) {
   SEA_CHECK_ARG(G && extra && B > 0 && C > 0 && (C % 4) == 0 && h > 0 && w > 0);
   // the 3x3 coarse window per tap covers 4 consecutive sample positions only for factors >= 3
   SEA_CHECK_ARG((int64_t)H >= 3 * (int64_t)h && (int64_t)W >= 3 * (int64_t)w);
@@ -355,13 +356,8 @@ extern "C" int sea_tap_gather_fwd(const float* G, float* extra, int accumulate, 
   const int64_t total = (int64_t)B * nBh * nBw * (C / 4);
   // the kernel indexes inside one image with 32-bit offsets
   SEA_CHECK_ARG((int64_t)H * W * (C / 4) < (1ll << 31) && (int64_t)h * w * 9 * (C / 4) < (1ll << 31));
-  static const int general_only = [] {   // looked up once: this launcher is on the attack's per-iteration path
-    const char* e = getenv("SEA_UPSAMPLE_GENERAL");
-    return (e && e[0] == '1') ? 1 : 0;
-  }();
-  // A/B (env SEA_TAP_INNER=0, read per call): the compile-time-weight path of interior blocks off
-  const char* tie = getenv("SEA_TAP_INNER");
-  const int inner_ok = (tie && tie[0] == '0') ? 0 : 1;
+  const int general_only = process_config().upsample_general;
+  const int inner_ok = inner ? 1 : 0;
 #define SEA_LAUNCH_TAP_FWD(SS)                                                                                          \
   hipLaunchKernelGGL(tap_gather_fwd_kernel<SS>, dim3(grid_for_xcd(total, 256)), dim3(256), 0, (hipStream_t)stream,      \
                      (const float4*)G, (float4*)extra, accumulate, C / 4, h, w, H, W, (float)h / (float)H,              \
@@ -382,10 +378,7 @@ extern "C" int sea_tap_gather_bwd(const float* gz, float* dG, int B, int C, int 
   SEA_CHECK_ARG(gz && dG && B > 0 && C > 0 && (C % 4) == 0 && h > 0 && w > 0 && H >= h && W >= w);
   SEA_CHECK_ARG(((((uintptr_t)gz) | ((uintptr_t)dG)) & 15) == 0);
   const int64_t total = (int64_t)B * h * w * (C / 4);
-  static const int general_only = [] {
-    const char* e = getenv("SEA_UPSAMPLE_GENERAL");
-    return (e && e[0] == '1') ? 1 : 0;
-  }();
+  const int general_only = process_config().upsample_general;
   if (!general_only && (int64_t)h * 4 == H && (int64_t)w * 4 == W) {
     hipLaunchKernelGGL(tap_gather_bwd_pow2_kernel<4>, dim3(grid_for_xcd(total, 256)), dim3(256), 0, (hipStream_t)stream,
                        (const float4*)gz, (float4*)dG, C / 4, h, w, total, xcd_order_enabled(), divs3(C / 4, w, h));

@@ -2,7 +2,6 @@
 // helpers, the LDS swizzle, the kernel argument block and the GELU formulas of M8.
 #pragma once
 #include "sea_common.h"
-#include <atomic>
 
 namespace sea {
 

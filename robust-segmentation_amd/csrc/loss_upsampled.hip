@@ -709,11 +709,8 @@ __global__ __launch_bounds__(256) void loss_upsampled_pow2_combine(const float* 
   }
 }
 
-static int ups2_scale(int h, int wl, int H, int W, int C) {
-  static const bool on = [] {
-    const char* e = getenv("SEA_K2U_POW2");
-    return !(e && e[0] == '0');
-  }();
+// on: the caller's pow2 flag (0 = the general gather kernel for every factor)
+static int ups2_scale(int h, int wl, int H, int W, int C, int on) {
   if (!on || C > 192 || h < 2 || wl < 2) return 0;
   if (H == 4 * h && W == 4 * wl) return 4;
   if (H == 16 * h && W == 16 * wl) return 16;
@@ -754,11 +751,11 @@ static bool plan_upsampled(int C, int h, int wl, int H, int W, UpsPlan* out) {
 
 using namespace sea;
 
-extern "C" size_t sea_loss_upsampled_workspace_bytes(int B, int C, int h, int w, int H, int W) {
+extern "C" size_t sea_loss_upsampled_workspace_bytes(int B, int C, int h, int w, int H, int W, int pow2) {
   UpsPlan p;
   if (B <= 0 || !plan_upsampled(C, h, w, H, W, &p)) return 0;
   const size_t v1 = (size_t)B * p.tiles_x * p.tiles_y * sizeof(BlockPartialU);
-  const int S = ups2_scale(h, w, H, W, C);
+  const int S = ups2_scale(h, w, H, W, C, pow2);
   if (!S) return v1;
   const size_t v2 = ups2_rec_bytes(B, h, w, S) + ups2_main_bytes(B, C, h, w) + ups2_lead_bytes(B, C, h, w, S);
   return v2 > v1 ? v2 : v1;
@@ -786,7 +783,7 @@ extern "C" int sea_loss_fwd_bwd_upsampled(const float* low, const void* y, int y
                                           int track_mode, int B, int C, int h, int wl, int H, int W, float grad_scale,
                                           float* dlow, void* pred, int pred_bytes, void* workspace,
                                           size_t workspace_bytes, float* loss_sum, float* track_sum,
-                                          int32_t* n_correct, void* stream) {
+                                          int32_t* n_correct, int pow2, void* stream) {
   SEA_CHECK_ARG(low && y && workspace && loss_sum && track_sum && n_correct);
   SEA_CHECK_ARG(B > 0 && B <= 65535 && C > 0 && h > 0 && wl > 0 && H >= h && W >= wl);
   SEA_CHECK_ARG(mode >= 0 && mode <= 3 && track_mode >= 0 && track_mode <= 3);
@@ -798,7 +795,7 @@ extern "C" int sea_loss_fwd_bwd_upsampled(const float* low, const void* y, int y
   SEA_CHECK_ARG(plan_upsampled(C, h, wl, H, W, &p));
   SEA_CHECK_ARG(workspace_bytes >= (size_t)B * p.tiles_x * p.tiles_y * sizeof(BlockPartialU));
   SEA_CHECK_ARG((((uintptr_t)workspace) & 15) == 0);
-  if (const int S = ups2_scale(h, wl, H, W, C)) {
+  if (const int S = ups2_scale(h, wl, H, W, C, pow2)) {
     const size_t need = ups2_rec_bytes(B, h, wl, S) + ups2_main_bytes(B, C, h, wl) + ups2_lead_bytes(B, C, h, wl, S);
     if (workspace_bytes >= need) {       // (a caller with the general kernel's smaller workspace keeps the general kernel)
       Ups2Args a;

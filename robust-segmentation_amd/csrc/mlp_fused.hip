@@ -222,7 +222,7 @@ constexpr int mlp_lds_bytes(int C, int waves, bool bwd) {
   return a > b ? a : b;
 }
 
-template <int C, int WAVES, bool BWD, bool PIPE, bool STAMP = false, int MLP_EPS = 4>
+template <int C, int WAVES, bool BWD, bool PIPE, bool STAMP = false>
 __global__ __launch_bounds__(WAVES * 64, (C <= 96 ? 8 : 4) / 4) void mlp_fused_kernel(const MlpArgs p) {
   constexpr int T = WAVES * 64;
   constexpr int KS = C / 16;             // 16-deep steps of the products that contract over C
@@ -519,7 +519,7 @@ __global__ __launch_bounds__(WAVES * 64, (C <= 96 ? 8 : 4) / 4) void mlp_fused_k
       // the exchange), each pinned behind its share of the MFMAs: a wave's matrix instructions run in the shadow of its own
       // vector work instead of in a phase of their own (left to itself the scheduler issues them in two clusters around ~700
       // vector instructions, and the two waves of a SIMD take turns: profiles/r6_mlp_fused_stamps.log)
-      constexpr int EPS = MLP_EPS;         // elements per micro-step (2 or 4 independent dependency chains)
+      constexpr int EPS = 4;               // elements per micro-step (independent dependency chains)
       constexpr int SPQ = 2 + 4 * (4 / EPS);   // micro-steps per quad
       constexpr int NSTEP = 4 * SPQ + 1;
       float ev[16], ek[16], ep[16], eq[16];
@@ -756,11 +756,11 @@ __global__ __launch_bounds__(WAVES * 64, (C <= 96 ? 8 : 4) / 4) void mlp_fused_k
   }
 }
 
-template <int C, int WAVES, bool BWD, bool PIPE, bool STAMP = false, int EPS = 4>
+template <int C, int WAVES, bool BWD, bool PIPE, bool STAMP = false>
 static int mlp_launch(const MlpArgs& p, hipStream_t st) {
   constexpr int lds = mlp_lds_bytes(C, WAVES, BWD);
   static_assert(lds * mlp_blocks_per_cu(C, WAVES) <= 160 * 1024, "LDS of a compute unit");
-  auto k = mlp_fused_kernel<C, WAVES, BWD, PIPE, STAMP, EPS>;
+  auto k = mlp_fused_kernel<C, WAVES, BWD, PIPE, STAMP>;
   if (lds > 48 * 1024) {
     static bool attr_set_dev[64] = {};
     int dev = 0;
@@ -785,11 +785,6 @@ extern "C" int sea_probe_gelu_mismatches(unsigned long long* out, void* stream) 
   hipLaunchKernelGGL(gelu_compare_kernel, dim3(256 * 16), dim3(256), 0, (hipStream_t)stream, out);
   SEA_RETURN_LAST();
 }
-
-static const int g_mlp_eps = [] {   // (A/B knob: elements per micro-step of the element-wise work, 2 or 4)
-  const char* e = getenv("SEA_MLP_EPS");
-  return (e && e[0] == '2') ? 2 : 4;
-}();
 
 extern "C" int sea_probe_ln_rows(const float* x, const float* ln_w, const float* ln_b, float eps, int M, int C, float* yn, float* mean,
                                  float* rstd, void* stream) {
@@ -821,7 +816,6 @@ static int mlp_fwd_impl(const float* x, int64_t ldx, const void* W1p, const floa
   SEA_CHECK_ARG(mlp_common_ok(p, C) && amax_h != nullptr);
   SEA_CHECK_ARG((((uintptr_t)b2) & 15) == 0 && (!res || ((ldres % 4) == 0 && ldres >= C && (((uintptr_t)res) & 15) == 0)));
   const hipStream_t st = (hipStream_t)stream;
-  if (g_mlp_eps == 2) return C == 96 ? mlp_launch<96, 4, false, true, false, 2>(p, st) : mlp_launch<192, 4, false, true, false, 2>(p, st);
   if (C == 96) return mlp_launch<96, 4, false, true>(p, st);
   return mlp_launch<192, 4, false, true>(p, st);
 }
@@ -851,7 +845,6 @@ static int mlp_bwd_impl(const float* g, int64_t ldg, const float* x, int64_t ldx
   SEA_CHECK_ARG(mlp_common_ok(p, C) && g && W2tp && amax_mul_dev && (ldg % 4) == 0 && ldg >= C &&
                 ((((uintptr_t)g) | ((uintptr_t)W2tp)) & 15) == 0);
   const hipStream_t st = (hipStream_t)stream;
-  if (g_mlp_eps == 2) return C == 96 ? mlp_launch<96, 4, true, false, false, 2>(p, st) : mlp_launch<192, 4, true, true, false, 2>(p, st);
   if (C == 96) return mlp_launch<96, 4, true, false>(p, st);
   return mlp_launch<192, 4, true, true>(p, st);
 }

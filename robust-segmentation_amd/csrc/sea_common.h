@@ -37,13 +37,17 @@ static inline int grid_for(int64_t work_items, int block) {
 // shared pixel once per XCD from the fabric.  xcd_range() gives XCD k the k-th contiguous eighth of the linear index
 // space (one image at B = 8) and lets the blocks that landed on that XCD stride through it: overlapping reads meet in
 // one L2.  The launch must use grid_for_xcd() (a multiple of 8 blocks).  SEA_XCD_ORDER=0 restores the plain order.
-static inline int xcd_order_enabled() {
-  static const int on = [] {
-    const char* e = getenv("SEA_XCD_ORDER");
-    return (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 1;
-  }();
-  return on;
-}
+//
+// The library's only configuration that is not an argument of a call: two A/B switches that dozens of launchers consult.  Read
+// from the environment once, at first use, and never written again (api_misc.cpp, the one place the library reads the
+// environment); sea_process_config() reports it.
+struct ProcessConfig {
+  int xcd_order;         // SEA_XCD_ORDER = 0 | 1 | 2: XCD-aware block order off / on (default) / also for the pure-stream kernels
+  int upsample_general;  // SEA_UPSAMPLE_GENERAL = 1: the general-ratio bilinear kernels even for power-of-two factors
+};
+const ProcessConfig& process_config();
+
+static inline int xcd_order_enabled() { return process_config().xcd_order; }
 
 static inline int grid_for_xcd(int64_t work_items, int block) {
   const int g = grid_for(work_items, block);

@@ -463,13 +463,7 @@ static inline int pow2_factor(int h, int w, int H, int W) {
   return 0;
 }
 
-static inline int upsample_general_only() {
-  static const int on = [] {
-    const char* e = getenv("SEA_UPSAMPLE_GENERAL");
-    return (e && e[0] == '1') ? 1 : 0;
-  }();
-  return on;
-}
+static inline int upsample_general_only() { return process_config().upsample_general; }
 
 // ---- channels_last variants: x (B,h,w,C), y (B,H,W,C), C % 4 == 0 ------------------------------------------
 // Lanes run along the channel dimension (16-byte accesses, perfectly coalesced); no LDS.  The UperNet head
@@ -755,20 +749,12 @@ extern "C" int sea_upsample_bilinear_fwd(const float* x, float* y, int64_t plane
   const int S = upsample_general_only() ? 0 : pow2_factor(h, w, H, W);
   if (S && (((uintptr_t)y) & 15) == 0) {  // float4 stores: W % 4 == 0 and a 16-byte aligned base
     if ((W & 3) == 0) {
-      static const int lanes_only = [] {
-        const char* e = getenv("SEA_UPSAMPLE_FWD");
-        return (e && e[0] == 'l') ? 1 : 0;  // "lane": one float4 per lane (A/B against the cell variant)
-      }();
-      if (S >= 4 && !lanes_only) {
+      if (S >= 4) {
         const int64_t total = planes * (h + 1) * (W / 4);
         const dim3 grid(grid_for_xcd(total, 256)), block(256);
         const int xo = xcd_order_enabled() == 2;
         const FastDiv fW4 = fast_div((uint32_t)(W / 4)), fC = fast_div((uint32_t)(h + 1));
-        static const int nt_mode = [] {  // SEA_UPSAMPLE_NT=0 / 1: never / always; default: by output size
-          const char* e = getenv("SEA_UPSAMPLE_NT");
-          return (e && (e[0] == '0' || e[0] == '1')) ? e[0] - '0' : 2;
-        }();
-        const int nt = nt_mode == 2 ? (planes * H * W * 4 > (192ll << 20)) : nt_mode;
+        const int nt = planes * H * W * 4 > (192ll << 20);   // non-temporal stores by output size
         switch (S) {
           case 4: hipLaunchKernelGGL(upsample_fwd_cells_kernel<4>, grid, block, 0, s, x, y, h, w, total, xo, fW4, fC, nt); break;
           case 8: hipLaunchKernelGGL(upsample_fwd_cells_kernel<8>, grid, block, 0, s, x, y, h, w, total, xo, fW4, fC, nt); break;
@@ -776,18 +762,13 @@ extern "C" int sea_upsample_bilinear_fwd(const float* x, float* y, int64_t plane
         }
         SEA_RETURN_LAST();
       }
-      const int64_t total = planes * H * (W / 4);
+      const int64_t total = planes * H * (W / 4);   // S == 2: one float4 per lane
       const dim3 grid(grid_for_xcd(total, 256)), block(256);
       // a pure output stream (the input is S^2 times smaller): the plain block order measured 10 % faster than the
       // XCD-contiguous one (151 planes x 8, 128 -> 512: 341 vs 379 us); SEA_XCD_ORDER=2 forces the latter
       const int xo = xcd_order_enabled() == 2;
       const FastDiv fW4 = fast_div((uint32_t)(W / 4)), fH = fast_div((uint32_t)H);
-      switch (S) {
-        case 2: hipLaunchKernelGGL(upsample_fwd_pow2_kernel<2>, grid, block, 0, s, x, y, h, w, total, xo, fW4, fH); break;
-        case 4: hipLaunchKernelGGL(upsample_fwd_pow2_kernel<4>, grid, block, 0, s, x, y, h, w, total, xo, fW4, fH); break;
-        case 8: hipLaunchKernelGGL(upsample_fwd_pow2_kernel<8>, grid, block, 0, s, x, y, h, w, total, xo, fW4, fH); break;
-        default: hipLaunchKernelGGL(upsample_fwd_pow2_kernel<16>, grid, block, 0, s, x, y, h, w, total, xo, fW4, fH); break;
-      }
+      hipLaunchKernelGGL(upsample_fwd_pow2_kernel<2>, grid, block, 0, s, x, y, h, w, total, xo, fW4, fH);
       SEA_RETURN_LAST();
     }
   }
@@ -807,12 +788,8 @@ extern "C" int sea_upsample_bilinear_bwd(const float* gy, float* gx, int64_t pla
     const int S = upsample_general_only() ? 0 : pow2_factor(h, w, H, W);
     // vector loads of min(4, S/2) floats at multiples of S/2 floats from the row start: rows must keep that alignment
     const int VL = S / 2 >= 4 ? 4 : S / 2;
-    static const int gather_only = [] {
-      const char* e = getenv("SEA_UPSAMPLE_BWD");
-      return (e && e[0] == 'g') ? 1 : 0;
-    }();
     const int cols = W / 4;
-    if (S && !gather_only && (W & 3) == 0 && (cols == 32 || cols == 64 || cols == 128 || cols == 256) &&
+    if (S && (W & 3) == 0 && (cols == 32 || cols == 64 || cols == 128 || cols == 256) &&
         (((uintptr_t)gy) & 15) == 0 && planes < (1 << 24)) {
       int lcols = 5;
       while ((1 << lcols) < cols) ++lcols;
@@ -878,11 +855,7 @@ extern "C" int sea_upsample_bilinear_nhwc_fwd(const float* x, const float* resid
                      (hipStream_t)stream, (const float4*)x, (const float4*)residual, (float4*)y, C / 4, h, w, H, W,     \
                      (float)h / (float)H, (float)w / (float)W, total, y_pixel_stride / 4, xcd_order_enabled(),          \
                      divs3(C / 4, W, H))
-  static const int lanes_only = [] {
-    const char* e = getenv("SEA_UPSAMPLE_FWD");
-    return (e && e[0] == 'l') ? 1 : 0;
-  }();
-  if ((S == 2 || S == 4 || S == 8) && !lanes_only) {
+  if (S == 2 || S == 4 || S == 8) {
     const int64_t cells = (int64_t)B * (h + 1) * (w + 1) * (C / 4);
 #define SEA_LAUNCH_NHWC_FWD_CELLS(SS)                                                                                   \
   hipLaunchKernelGGL(upsample_nhwc_fwd_cells_kernel<SS>, dim3(grid_for_xcd(cells, 256)), dim3(256), 0,                  \
@@ -898,13 +871,7 @@ extern "C" int sea_upsample_bilinear_nhwc_fwd(const float* x, const float* resid
 #undef SEA_LAUNCH_NHWC_FWD_CELLS
     SEA_RETURN_LAST();
   }
-  switch (S) {
-    case 2: SEA_LAUNCH_NHWC_FWD(2); break;
-    case 4: SEA_LAUNCH_NHWC_FWD(4); break;
-    case 8: SEA_LAUNCH_NHWC_FWD(8); break;
-    case 16: SEA_LAUNCH_NHWC_FWD(16); break;
-    default: SEA_LAUNCH_NHWC_FWD(0); break;
-  }
+  if (S == 16) SEA_LAUNCH_NHWC_FWD(16); else SEA_LAUNCH_NHWC_FWD(0);
 #undef SEA_LAUNCH_NHWC_FWD
   SEA_RETURN_LAST();
 }

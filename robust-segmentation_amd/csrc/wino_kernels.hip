@@ -371,12 +371,6 @@ __global__ __launch_bounds__(256) void wino_filter_kernel(const float* __restric
 
 using namespace sea;
 
-// A/B (env SEA_WINO_IN_VEC4, read per call): 1 = the F(4,3) input transform with four channels per lane
-static inline int wino_in_vec4() {
-  const char* e = getenv("SEA_WINO_IN_VEC4");
-  return e ? atoi(e) : 1;
-}
-
 static bool wino_dims(int B, int C, int H, int W, int m, int vec, int* nTh, int* nTw, int64_t* T) {
   if (!(B > 0 && C > 0 && H > 0 && W > 0 && (m == 2 || m == 4) && (C % vec) == 0)) return false;
   *nTh = (H + m - 1) / m;
@@ -391,25 +385,26 @@ extern "C" int64_t sea_wino_tiles(int B, int H, int W, int m) {
 }
 
 static int wino_input_impl(const float* x, int64_t x_pixel_stride, const float* gate, const float* scale, float* V,
-                           int64_t v_tile_stride, int B, int C, int H, int W, int m, uint32_t* amax_out, void* stream);
+                           int64_t v_tile_stride, int B, int C, int H, int W, int m, int vec4, uint32_t* amax_out, void* stream);
 
 extern "C" int sea_wino_input_transform(const float* x, int64_t x_pixel_stride, const float* gate, const float* scale,
-                                        float* V, int64_t v_tile_stride, int B, int C, int H, int W, int m,
+                                        float* V, int64_t v_tile_stride, int B, int C, int H, int W, int m, int vec4,
                                         void* stream) {
-  return wino_input_impl(x, x_pixel_stride, gate, scale, V, v_tile_stride, B, C, H, W, m, nullptr, stream);
+  return wino_input_impl(x, x_pixel_stride, gate, scale, V, v_tile_stride, B, C, H, W, m, vec4, nullptr, stream);
 }
 
 // same, and the float bits of max |V| are max-accumulated into *amax_out (a pre-zeroed device word; several calls that fill
 // channel slices of one V may share it): the activation scale of sea_gemm_split_f16 without another pass over V
 extern "C" int sea_wino_input_transform_amax(const float* x, int64_t x_pixel_stride, const float* gate, const float* scale,
-                                             float* V, int64_t v_tile_stride, int B, int C, int H, int W, int m,
+                                             float* V, int64_t v_tile_stride, int B, int C, int H, int W, int m, int vec4,
                                              uint32_t* amax_out, void* stream) {
   SEA_CHECK_ARG(amax_out != nullptr);
-  return wino_input_impl(x, x_pixel_stride, gate, scale, V, v_tile_stride, B, C, H, W, m, amax_out, stream);
+  return wino_input_impl(x, x_pixel_stride, gate, scale, V, v_tile_stride, B, C, H, W, m, vec4, amax_out, stream);
 }
 
+// vec4 (m = 4 only): non-zero = the F(4,3) transform with four channels per lane (shipped), 0 = two (A/B)
 static int wino_input_impl(const float* x, int64_t x_pixel_stride, const float* gate, const float* scale, float* V,
-                           int64_t v_tile_stride, int B, int C, int H, int W, int m, uint32_t* amax_out, void* stream) {
+                           int64_t v_tile_stride, int B, int C, int H, int W, int m, int vec4, uint32_t* amax_out, void* stream) {
   int nTh, nTw;
   int64_t T;
   SEA_CHECK_ARG(x && V && wino_dims(B, C, H, W, m, 4, &nTh, &nTw, &T));
@@ -421,7 +416,7 @@ static int wino_input_impl(const float* x, int64_t x_pixel_stride, const float* 
     hipLaunchKernelGGL((wino_input_kernel<2, 4>), dim3(grid_for_xcd(total, 256)), dim3(256), 0, (hipStream_t)stream, x, gate,
                        scale, V, C, H, W, nTh, nTw, T, total, x_pixel_stride, v_tile_stride, xcd_order_enabled() == 2, divs3(C / 4, nTw, nTh),
                        amax_out);
-  } else if (wino_in_vec4() & 1) {
+  } else if (vec4) {
     const int64_t total = T * (C / 4);
     hipLaunchKernelGGL((wino_input_cols_kernel<4, 4>), dim3(grid_for_xcd(total, 256)), dim3(256), 0, (hipStream_t)stream, x, gate,
                        scale, V, C, H, W, nTh, nTw, T, total, x_pixel_stride, v_tile_stride, xcd_order_enabled() == 2, divs3(C / 4, nTw, nTh),
@@ -436,7 +431,7 @@ static int wino_input_impl(const float* x, int64_t x_pixel_stride, const float* 
 }
 
 extern "C" int sea_wino_output_transform(const float* Mx, const float* addend, const float* scale, const float* bias,
-                                         int relu, float* y, int B, int C, int H, int W, int m, void* stream) {
+                                         int relu, float* y, int B, int C, int H, int W, int m, int vec4, void* stream) {
   int nTh, nTw;
   int64_t T;
   SEA_CHECK_ARG(Mx && y && wino_dims(B, C, H, W, m, 4, &nTh, &nTw, &T));
@@ -445,7 +440,7 @@ extern "C" int sea_wino_output_transform(const float* Mx, const float* addend, c
     const int64_t total = T * (C / 4);
     hipLaunchKernelGGL((wino_output_kernel<2, 4>), dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, Mx,
                        addend, scale, bias, relu, y, C, H, W, nTh, nTw, T, total, divs3(C / 4, nTw, nTh));
-  } else if (wino_in_vec4() & 2) {     // (A/B bit 2: four channels per lane in the output transform too)
+  } else if (vec4) {     // (A/B: four channels per lane in the output transform too)
     const int64_t total = T * (C / 4);
     hipLaunchKernelGGL((wino_output_kernel<4, 4>), dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, Mx,
                        addend, scale, bias, relu, y, C, H, W, nTh, nTw, T, total, divs3(C / 4, nTw, nTh));

@@ -21,7 +21,7 @@ LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
 
 _lib = None
 
-_vp, _i, _i64, _f, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
+_vp, _i, _i64, _f, _sz, _u = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t, C.c_uint
 _SIGS = {
     "sea_abi_version": (C.c_int, []),
     "sea_build_info": (C.c_char_p, []),
@@ -37,9 +37,9 @@ _SIGS = {
                               _vp, _vp, _vp, _vp]),
     "sea_loss_fwd_bwd_tuned": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i64, _f, _vp, _vp, _i, _vp, _vp,
                                     _sz, _vp, _vp, _vp, _vp, _i]),
-    "sea_loss_upsampled_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "sea_loss_upsampled_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "sea_loss_fwd_bwd_upsampled": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp, _sz, _vp,
-                                        _vp, _vp, _vp]),
+                                        _vp, _vp, _i, _vp]),
     "sea_class_counts": (_i, [_vp, _i, _vp, _i, _i, _i, _i64, _i, _i, _vp, _vp, _vp, _vp]),
     "sea_confusion": (_i, [_vp, _i, _vp, _i, _i64, _i, _vp, _vp]),
     "sea_apgd_track": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -54,8 +54,8 @@ _SIGS = {
     "sea_count_ignored": (_i, [_vp, _i, _i, _i64, _vp, _vp]),
     "sea_worst_miou_greedy": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "sea_dwconv7x7": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "sea_dwconv7x7_nhwc": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "sea_dwconv7x7_nhwc_add": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "sea_dwconv7x7_nhwc": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _u, _vp]),
+    "sea_dwconv7x7_nhwc_add": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _u, _vp]),
     "sea_nchw_to_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i64, _vp]),
     "sea_nhwc_to_nchw": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i64, _vp]),
     "sea_upsample_bilinear_fwd": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp]),
@@ -71,18 +71,15 @@ _SIGS = {
     "sea_ln_gelu_cl_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _f, _vp]),
     "sea_ln_gelu_cl_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i64, _f, _vp]),
     "sea_wino_tiles": (_i64, [_i, _i, _i, _i]),
-    "sea_wino_input_transform": (_i, [_vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
+    "sea_wino_input_transform": (_i, [_vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp]),
     "sea_wino_filter_transform": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
-    "sea_wino_output_transform": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
-    "sea_tap_gather_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "sea_wino_output_transform": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "sea_tap_gather_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "sea_tap_gather_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "sea_gate_scale": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp]),
     "sea_upsample_bilinear_nhwc_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i64, _vp]),
     "sea_upsample_bilinear_nhwc_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i64, _vp]),
     "sea_patch2x2": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "sea_attention_fwd": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
-    "sea_attention_bwd": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                               _i64, _i64, _i64, _vp]),
     "sea_attention_bwd_terms": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                      _i64, _i64, _i64, _i, _vp]),
     "sea_attention_fwd_terms": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp]),
@@ -90,13 +87,13 @@ _SIGS = {
     "sea_attention_bwd_f16": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                    _i64, _i64, _i64, _vp]),
     "sea_absmax_bits": (_i, [_vp, _i64, _i, _i, _i, _i64, _i, _vp, _vp]),
-    "sea_gemm_split_f16": (_i, [_vp, _i64, _vp, _vp, _i64, _vp, _i, _i, _i, _i, _i, _i64, _i64, _i64, _vp, _i, _vp, _vp]),
-    "sea_wino_input_transform_amax": (_i, [_vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp, _vp]),
-    "sea_gemm_split_fused": (_i, [_vp, _i64, _vp, _vp, _i64, _vp, _i, _i, _i, _i, _i, _i, _i64, _i64, _i64, _vp, _i, _vp, _vp, _vp]),
+    "sea_gemm_split_f16": (_i, [_vp, _i64, _vp, _vp, _i64, _vp, _i, _i, _i, _i, _i, _i64, _i64, _i64, _vp, _i, _vp, _u, _vp]),
+    "sea_wino_input_transform_amax": (_i, [_vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "sea_gemm_split_fused": (_i, [_vp, _i64, _vp, _vp, _i64, _vp, _i, _i, _i, _i, _i, _i, _i64, _i64, _i64, _vp, _i, _vp, _vp, _u, _vp]),
     "sea_gemm_splitk_reduce": (_i, [_vp, _i, _i, _i, _vp, _vp, _i64, _i, _vp, _i64, _vp, _vp]),
     "sea_gemm_split_packed_bytes": (_i64, [_i, _i, _i]),
     "sea_gemm_split_pack": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _vp]),
-    "sea_gemm_split": (_i, [_vp, _i64, _vp, _vp, _i64, _vp, _i, _i, _i, _i, _i, _i, _i64, _i64, _i64, _vp]),
+    "sea_gemm_split": (_i, [_vp, _i64, _vp, _vp, _i64, _vp, _i, _i, _i, _i, _i, _i, _i64, _i64, _i64, _u, _vp]),
     "sea_mlp_fused_supported": (_i, [_i, _i]),
     "sea_classifier_supported": (_i, [_i, _i, _i]),
     "sea_classifier_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
@@ -108,8 +105,7 @@ _SIGS = {
     "sea_mlp_fused_bwd": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp]),
     "sea_ln_mlp_fused_fwd": (_i, [_vp, _i64, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i, _i, _i, _vp, _vp, _vp]),
     "sea_ln_mlp_fused_bwd": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp]),
-    "sea_gemm_split_mfma_shape": (_i, [_i]),
-    "sea_gemm_split_pipeline": (_i, [_i]),
+    "sea_process_config": (_i, [_i]),
     "sea_probe_stream_copy": (_i, [_vp, _vp, _sz, _i, _vp]),
     "sea_probe_stream_read": (_i, [_vp, _vp, _sz, _vp]),
     "sea_msf_resize_input": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
@@ -311,8 +307,9 @@ def loss_fwd_bwd(logits, y, weights, mode: int, track_mode: int, grad_scale: flo
 
 
 def loss_fwd_bwd_upsampled(low, y, weights, mode: int, track_mode: int, grad_scale: float, want_grad: bool = True,
-                           pred=None, workspace=None, out=None, dlow=None):
-    """Run K2u on LOW-RES logits (B,C,h,w); labels / pred are at the full resolution of `y`."""
+                           pred=None, workspace=None, out=None, dlow=None, pow2: bool = True):
+    """Run K2u on LOW-RES logits (B,C,h,w); labels / pred are at the full resolution of `y`.  ``pow2`` = False keeps the
+    general gather kernel at the factors 4 and 16 too (A/B; the caller owns the switch: semseg.attacker.K2U_POW2)."""
     _dev(low, y, weights, pred)
     low = _f32c(low)
     B, Cc, h, w = low.shape
@@ -322,7 +319,7 @@ def loss_fwd_bwd_upsampled(low, y, weights, mode: int, track_mode: int, grad_sca
     dev = low.device
     L = lib()
     if workspace is None:
-        nb = L.sea_loss_upsampled_workspace_bytes(B, Cc, h, w, H, W)
+        nb = L.sea_loss_upsampled_workspace_bytes(B, Cc, h, w, H, W, int(bool(pow2)))
         if nb == 0:
             raise SeaNativeError("no K2u tiling for this shape")
         workspace = torch.empty(nb, dtype=torch.uint8, device=dev)
@@ -338,7 +335,7 @@ def loss_fwd_bwd_upsampled(low, y, weights, mode: int, track_mode: int, grad_sca
     _check(L.sea_loss_fwd_bwd_upsampled(_p(low), _p(y), int_bytes(y), _p(weights), mode, track_mode, B, Cc, h, w, H, W,
                                         grad_scale, _p(dlow), _p(pred), 0 if pred is None else int_bytes(pred),
                                         _p(workspace), workspace.numel(), _p(out[0]), _p(out[1]), _p(out[2]),
-                                        _stream()), "sea_loss_fwd_bwd_upsampled")
+                                        int(bool(pow2)), _stream()), "sea_loss_fwd_bwd_upsampled")
     return dict(dlogits=dlow, loss_sum=out[0], track_sum=out[1], n_correct=out[2], pred=pred)
 
 
@@ -824,6 +821,10 @@ def upsample_bilinear_backward_cl(gy, in_size):
 
 
 # ------------------------------------------------------------------------------------------------ M6
+# A/B switch (env SEA_TAP_INNER=0): the tap gather with run-time interpolation weights in interior blocks too
+TAP_INNER = os.environ.get("SEA_TAP_INNER", "1")[:1] != "0"
+
+
 def tap_gather(G, size, extra=None):
     """G (B,h,w,9,C) coarse per-tap maps -> (B,C,H,W) channels_last: sum over the 3x3 taps of the shifted
     bilinear up-samplings (added to ``extra`` in place when given)."""
@@ -837,7 +838,8 @@ def tap_gather(G, size, extra=None):
         extra = torch.empty(B, Cc, H, W, dtype=torch.float32, device=G.device, memory_format=torch.channels_last)
     elif tuple(extra.shape) != (B, Cc, H, W) or cl_pixel_stride(extra) != Cc:
         raise SeaNativeError("tap_gather: extra must be a dense channels_last (B,C,H,W) float32 tensor")
-    _check(lib().sea_tap_gather_fwd(_p(_f32c(G)), _p(extra), int(acc), B, Cc, h, w, H, W, _stream()), "sea_tap_gather_fwd")
+    _check(lib().sea_tap_gather_fwd(_p(_f32c(G)), _p(extra), int(acc), B, Cc, h, w, H, W, int(TAP_INNER), _stream()),
+           "sea_tap_gather_fwd")
     return extra
 
 
@@ -1010,6 +1012,9 @@ def wino_filter(weight, m: int, flip: bool):
 # many partners its batch has (a sharded evaluation equals the unsharded one bit for bit).  16 = a 16 x 16 map at F(4,3):
 # the PSP bottleneck (2816 -> 512) of a 512 x 512 input, 145 + 164 us on the library against ~85 + ~85 us here.
 WINO_SPLIT_MIN_TILES = int(os.environ.get("SEA_WINO_SPLIT_MIN_TILES", "16"))
+# A/B switch (env SEA_WINO_IN_VEC4, a bit mask): bit 0 = the F(4,3) input transform with four channels per lane (shipped; 0 =
+# two), bit 1 = the output transform with four channels per lane as well
+WINO_IN_VEC4 = int(os.environ.get("SEA_WINO_IN_VEC4", "1"))
 
 
 def wino_conv3x3_cl(x, U, m: int, bias=None, scale=None, relu: bool = False, gate=None, gate_scale=None,
@@ -1044,10 +1049,11 @@ def wino_conv3x3_cl(x, U, m: int, bias=None, scale=None, relu: bool = False, gat
     for t, xps in zip(xs, strides):
         if v_amax is not None:
             _check(L.sea_wino_input_transform_amax(_p(t), xps, _p(gate), _p(gate_scale), V.data_ptr() + 4 * off, Cin, B,
-                                                   t.shape[1], H, W, m, _p(v_amax), _stream()), "sea_wino_input_transform_amax")
+                                                   t.shape[1], H, W, m, WINO_IN_VEC4 & 1, _p(v_amax), _stream()),
+                   "sea_wino_input_transform_amax")
         else:
             _check(L.sea_wino_input_transform(_p(t), xps, _p(gate), _p(gate_scale), V.data_ptr() + 4 * off, Cin, B, t.shape[1],
-                                              H, W, m, _stream()), "sea_wino_input_transform")
+                                              H, W, m, WINO_IN_VEC4 & 1, _stream()), "sea_wino_input_transform")
         off += t.shape[1]
     if use_split:
         # M8: the (A*A) Winograd-domain products on the bf16 matrix cores (operands split into bf16 terms, fp32 accumulate)
@@ -1070,20 +1076,25 @@ def wino_conv3x3_cl(x, U, m: int, bias=None, scale=None, relu: bool = False, gat
     if addend is not None and (tuple(addend.shape) != (B, Cout, H, W) or cl_pixel_stride(addend) != Cout):
         raise SeaNativeError("wino_conv3x3_cl: addend must be a dense channels_last (B,Cout,H,W) float32 tensor")
     _check(L.sea_wino_output_transform(_p(Mx), _p(addend), _p(scale), _p(bias), int(relu), _p(y), B, Cout, H, W, m,
-                                       _stream()), "sea_wino_output_transform")
+                                       (WINO_IN_VEC4 >> 1) & 1, _stream()), "sea_wino_output_transform")
     return y
 
 
-def dwconv7x7_nhwc(x, wt, bias=None, flip: bool = False, addend=None):
+# A/B switches of the depthwise launcher (env SEA_DWCONV_AB, a bit mask: sea_dwconv7x7_nhwc in include/sea_hip.h; 0 = shipped)
+DWCONV_AB = int(os.environ.get("SEA_DWCONV_AB", "0"))
+
+
+def dwconv7x7_nhwc(x, wt, bias=None, flip: bool = False, addend=None, ab: int = None):
     """Depthwise 7x7 on a (B,H,W,C) contiguous tensor; wt is the (49,C) taps-major filter bank; ``addend`` (shape of
-    the result) is added after the taps (the skip gradient in the backward of a residual block)."""
+    the result) is added after the taps (the skip gradient in the backward of a residual block).  ``ab``: per-call override
+    of the launcher's A/B mask ``DWCONV_AB`` (every variant gives the same bits)."""
     _dev(x, wt, bias, addend)
     B, H, W, Cc = x.shape
     if addend is not None and (addend.shape != x.shape or addend.dtype != torch.float32 or not addend.is_contiguous()):
         raise SeaNativeError("dwconv7x7_nhwc: addend must be a contiguous float32 tensor of the input's shape")
     y = torch.empty_like(x)
     _check(lib().sea_dwconv7x7_nhwc_add(_p(_f32c(x)), _p(_f32c(wt)), _p(bias), _p(addend), _p(y), B, Cc, H, W, int(flip),
-                                        _stream()), "sea_dwconv7x7_nhwc_add")
+                                        DWCONV_AB if ab is None else int(ab), _stream()), "sea_dwconv7x7_nhwc_add")
     return y
 
 
@@ -1508,9 +1519,31 @@ def _amax_words(A3, M, K, G, sA, groups, per_row=False):
     return words, rpw
 
 
+# Which kernel runs behind sea_gemm_split* is an argument of every call (the `variant` word of include/sea_hip.h); the
+# process-wide defaults live here: env SEA_GEMM_PIPE = 0 | 1 | 3 forces one K-loop kernel everywhere (2 = chosen per launch),
+# SEA_GEMM_SHAPE=16 the 16x16x32 MFMA fragments.
+_e = os.environ.get("SEA_GEMM_PIPE", "")
+GEMM_PIPE = int(_e[0]) if _e[:1] in ("0", "1", "2", "3") else 2
+GEMM_MFMA_SHAPE = 16 if os.environ.get("SEA_GEMM_SHAPE", "")[:1] == "1" else 32
+del _e
+_GEMM_PIPE_BITS = {2: 0, 0: 1, 1: 2, 3: 3}   # SEA_GEMM_VARIANT_DEFAULT, SEA_GEMM_PIPE_SINGLE, _PINGPONG, _BIG
+_GEMM_SHAPE16 = 4                            # SEA_GEMM_SHAPE16
+
+
+def gemm_variant(pipe=None, mfma_shape=None) -> int:
+    """the `variant` word of sea_gemm_split* for a K-loop pipeline (0 | 1 | 2 | 3) and an MFMA fragment shape (16 | 32);
+    None = the module defaults GEMM_PIPE / GEMM_MFMA_SHAPE"""
+    pipe = GEMM_PIPE if pipe is None else int(pipe)
+    mfma_shape = GEMM_MFMA_SHAPE if mfma_shape is None else int(mfma_shape)
+    if pipe not in _GEMM_PIPE_BITS or mfma_shape not in (16, 32):
+        raise SeaNativeError("gemm_split: pipe must be 0, 1, 2 or 3 and mfma_shape 16 or 32")
+    return _GEMM_PIPE_BITS[pipe] | (_GEMM_SHAPE16 if mfma_shape == 16 else 0)
+
+
 def gemm_split(A, Wp: PackedWeight, bias=None, relu: bool = False, out=None, amax=None, out_amax=None, addend=None,
                gelu_out=None, gelu_grad_of=None, amax_rows: int = 0, groups: int = 1, a_gelu_grad_of=None,
-               a_gelu: bool = False, a_relu_gate=None, row_amax: bool = False, amax_mul: float = 1.0):
+               a_gelu: bool = False, a_relu_gate=None, row_amax: bool = False, amax_mul: float = 1.0, pipe=None,
+               mfma_shape=None):
     """out (.., N) = A (.., K) @ W^T [+ bias] [ReLU] with W pre-split (``gemm_split_pack``).  A: fp32, last dim
     contiguous; 2-D (M, K) with any 4-aligned row stride, or (G, M, K) against a batch of G packed weights.
     fp16 x 2 weights (terms 22): ``amax`` = device words holding the float bits of (upper bounds of) max|A|, one per
@@ -1524,9 +1557,11 @@ def gemm_split(A, Wp: PackedWeight, bias=None, relu: bool = False, out=None, ama
     GELU'(``gelu_grad_of``) (layout of out).  Prologue instead (exclusive): A is read as A * GELU'(``a_gelu_grad_of``)
     (same shape and strides as A; terms 2 or 22), as (``a_relu_gate`` > 0 ? A : 0) (same layout), or as GELU(A)
     (``a_gelu``).
+    ``pipe`` / ``mfma_shape``: per-call choice of the kernel (see ``gemm_variant``); every ``pipe`` gives the same bits.
     Split-K products (chosen here for small tile grids) go through ONE partial-product workspace per device: a caller that
     runs these GEMMs on several streams at once must order them itself, and a caller that captures them into a HIP graph
     must hold ``ksplit_workspace_pin(device)`` for as long as the graph may replay (``ApgdRun`` does both)."""
+    variant = gemm_variant(pipe, mfma_shape)
     gate = a_relu_gate is not None
     if gate:
         if a_gelu_grad_of is not None:
@@ -1573,7 +1608,7 @@ def gemm_split(A, Wp: PackedWeight, bias=None, relu: bool = False, out=None, ama
             shape, strides = (S, M, K // S), (K // S, A3.stride(1), 1)
             gemm_split(A3[0].as_strided(shape, strides), Wp.k_slices(S), out=part, amax=amax, amax_rows=amax_rows,
                        a_gelu_grad_of=None if (a_gelu_grad_of is None or gate) else a_gelu_grad_of.as_strided(shape, strides),
-                       a_gelu=a_gelu, amax_mul=mul_dev if mul_dev is not None else amax_mul,
+                       a_gelu=a_gelu, amax_mul=mul_dev if mul_dev is not None else amax_mul, pipe=pipe, mfma_shape=mfma_shape,
                        **({"a_relu_gate": a_gelu_grad_of.as_strided(shape, strides)} if gate else {}))
             _check(lib().sea_gemm_splitk_reduce(_p(part), S, M, Wp.N, _p(bias), _p(addend),
                                                 addend.stride(0) if addend is not None else 0, int(relu), _p(O3), O3.stride(1),
@@ -1585,7 +1620,7 @@ def gemm_split(A, Wp: PackedWeight, bias=None, relu: bool = False, out=None, ama
         out = gemm_split(A, Wp, bias=bias, relu=False, out=out, amax=amax, out_amax=None, amax_rows=amax_rows, groups=groups,
                          a_gelu_grad_of=None if gate else a_gelu_grad_of, a_gelu=a_gelu,
                          a_relu_gate=a_gelu_grad_of if gate else None, row_amax=row_amax,
-                         amax_mul=mul_dev if mul_dev is not None else amax_mul)
+                         amax_mul=mul_dev if mul_dev is not None else amax_mul, pipe=pipe, mfma_shape=mfma_shape)
         out += addend
         if relu:
             torch.relu_(out)
@@ -1618,7 +1653,7 @@ def gemm_split(A, Wp: PackedWeight, bias=None, relu: bool = False, out=None, ama
             amax, amax_rows = _amax_words(A3, M, K, G, sA, groups, row_amax)
         _check(lib().sea_gemm_split_fused(_p(A3), A3.stride(1), _p(Wp.data), _p(O3), O3.stride(1), _p(bias), int(relu), M, Wp.N,
                                           K, Wp.terms, G, sA, Wp.stride, sC, _p(amax) if Wp.terms == 22 else None, amax_rows,
-                                          _p(out_amax) if Wp.terms == 22 else None, C.addressof(epi), _stream()),
+                                          _p(out_amax) if Wp.terms == 22 else None, C.addressof(epi), variant, _stream()),
                "sea_gemm_split_fused")
         return out
     if Wp.terms == 22:
@@ -1626,9 +1661,9 @@ def gemm_split(A, Wp: PackedWeight, bias=None, relu: bool = False, out=None, ama
         if amax is None:
             amax, amax_rows = _amax_words(A3, M, K, G, sA, groups, row_amax)
         _check(lib().sea_gemm_split_f16(_p(A3), A3.stride(1), _p(Wp.data), _p(O3), O3.stride(1), _p(bias), int(relu), M, Wp.N,
-                                        K, G, sA, Wp.stride, sC, _p(amax), amax_rows, _p(out_amax), _stream()),
+                                        K, G, sA, Wp.stride, sC, _p(amax), amax_rows, _p(out_amax), variant, _stream()),
                "sea_gemm_split_f16")
         return out
     _check(lib().sea_gemm_split(_p(A3), A3.stride(1), _p(Wp.data), _p(O3), O3.stride(1), _p(bias), int(relu), M, Wp.N, K,
-                                Wp.terms, G, sA, Wp.stride, sC, _stream()), "sea_gemm_split")
+                                Wp.terms, G, sA, Wp.stride, sC, variant, _stream()), "sea_gemm_split")
     return out

@@ -285,6 +285,8 @@ _fu = os.environ.get("SEA_FUSE_UPSAMPLE", "auto")
 FUSE_UPSAMPLE = "auto" if _fu == "auto" else (_fu == "1")
 FUSE_UPSAMPLE_AUTO_BYTES = 24 * 2 ** 30
 FUSE_UPSAMPLE_MIN_CLASSES = 96
+# A/B switch (env SEA_K2U_POW2=0): K2u's general gather kernel at the factors 4 and 16 too (the one place it is read)
+K2U_POW2 = os.environ.get("SEA_K2U_POW2", "1")[:1] != "0"
 
 # HIP-graph replay of the middle iterations of an APGD run (see ApgdRun._capture).  SEA_HIP_GRAPH=0 disables it.
 USE_HIP_GRAPH = os.environ.get("SEA_HIP_GRAPH", "1") != "0"
@@ -369,7 +371,7 @@ class _RunBuffers:
     def k2u_workspace(self, low):
         if self.ws_low is None:
             self.ws_low = torch.empty(N.lib().sea_loss_upsampled_workspace_bytes(
-                low.shape[0], low.shape[1], low.shape[2], low.shape[3], self.x.shape[-2], self.x.shape[-1]),
+                low.shape[0], low.shape[1], low.shape[2], low.shape[3], self.x.shape[-2], self.x.shape[-1], int(K2U_POW2)),
                 dtype=torch.uint8, device=low.device)
         return self.ws_low
 
@@ -398,14 +400,14 @@ def _arith_signature(model):
     """Everything process-global that a captured forward / backward bakes in besides addresses and weights: the arithmetic
     and kernel switches of the model modules and of the kernel bindings (every UPPER-CASE scalar global of semseg.models.* and
     semseg._native: GEMM_TERMS, GEMM_TERMS_BWD, WINOGRAD_TILE, WINOGRAD_MIN_PIXELS, USE_*, FUSE_MLP, WINO_SPLIT_MIN_TILES ...;
-    the in-process override of the GEMM terms), the attention arithmetic (read per call from the environment), the library's
-    K-loop pipeline and MFMA shape, the autocast state and ``model.training``.  A cached pair whose signature differs is
-    captured again instead of replaying the old arithmetic."""
+    GEMM_PIPE, GEMM_MFMA_SHAPE, DWCONV_AB ...; the in-process override of the GEMM terms), the attention arithmetic (read per
+    call from the environment), this module's K2U_POW2, the autocast state and ``model.training``.  The library itself keeps no
+    switch: which kernel runs is an argument of every call.  A cached pair whose signature differs is captured again instead
+    of replaying the old arithmetic."""
     import sys
     sig = [bool(getattr(model, "training", False)), torch.is_autocast_enabled(),
            str(torch.get_autocast_dtype("cuda")) if torch.is_autocast_enabled() else None,
-           N.attn_terms_fwd(), N.attn_terms_bwd(), int(N.lib().sea_gemm_split_pipeline(-1)),
-           int(N.lib().sea_gemm_split_mfma_shape(0))]
+           N.attn_terms_fwd(), N.attn_terms_bwd(), K2U_POW2]
     for name in sorted(sys.modules):
         if name.startswith("semseg.models.") or name == N.__name__:
             mod = sys.modules[name]
@@ -515,7 +517,7 @@ class ApgdRun:
                 lo = probe[0]
                 pow2 = any(x.shape[-2] == r * lo.shape[-2] and x.shape[-1] == r * lo.shape[-1] for r in (4, 16))
                 fast = (pow2 and FUSE_UPSAMPLE_MIN_CLASSES <= lo.shape[1] <= 192 and lo.dtype == torch.float32
-                        and min(lo.shape[-2:]) >= 2 and os.environ.get("SEA_K2U_POW2", "1") != "0")
+                        and min(lo.shape[-2:]) >= 2 and K2U_POW2)
                 fuse_upsample = fast or full > FUSE_UPSAMPLE_AUTO_BYTES
         else:
             fuse_upsample = False
@@ -561,7 +563,7 @@ class ApgdRun:
         if self.fused:
             r = N.loss_fwd_bwd_upsampled(logits.detach().contiguous(), self.yc, self.w, self.mode, self.tmode,
                                          self.gscale, want_grad=want_grad, pred=o.pred, workspace=o.k2u_workspace(logits),
-                                         out=o.stats, dlow=o.dlogits if want_grad else None)
+                                         out=o.stats, dlow=o.dlogits if want_grad else None, pow2=K2U_POW2)
         else:
             r = N.loss_fwd_bwd(logits.detach(), self.yc, self.w, self.mode, self.tmode, self.gscale,
                                want_grad=want_grad, pred=o.pred, workspace=o.ws, out=o.stats,

@@ -381,7 +381,7 @@ def test_fp16x2_row_bound_carried_through_a_gemm(N):
 
 
 def test_mfma_shape_16_variants_match_shape_32(N):
-    """sea_gemm_split_mfma_shape(16): every kernel variant (three modes, bias / ReLU, the three prologues, the fused epilogue,
+    """mfma_shape=16 (the SEA_GEMM_SHAPE16 bit of the variant word, per call): every kernel variant (three modes, bias / ReLU, the three prologues, the fused epilogue,
     out_amax) on v_mfma_f32_16x16x32_* fragments gives the 32x32x16 result up to summation order, and the float64 reference
     to the same accuracy"""
     g = torch.Generator(device="cuda").manual_seed(21)
@@ -392,11 +392,11 @@ def test_mfma_shape_16_variants_match_shape_32(N):
     t = torch.randn(M, K, generator=g, device="cuda")
     add = torch.randn(M, Nn, generator=g, device="cuda")
 
-    def all_variants():
+    def all_variants(**v):
         outs = {}
         for terms in (22, 3, 2):
             Wp = N.gemm_split_pack(W, terms=terms)
-            kw = dict(row_amax=True) if terms == 22 else {}
+            kw = dict(row_amax=True, **v) if terms == 22 else dict(v)
             outs[terms, "plain"] = N.gemm_split(A, Wp, bias=bias, relu=True, **kw)
             outs[terms, "gelu"] = N.gemm_split(A, Wp, a_gelu=True, **kw)
             outs[terms, "addend"] = N.gemm_split(A, Wp, bias=bias, addend=add, **kw)
@@ -404,19 +404,12 @@ def test_mfma_shape_16_variants_match_shape_32(N):
                 outs[terms, "gelu_grad"] = N.gemm_split(A, Wp, a_gelu_grad_of=t, **kw)
                 outs[terms, "gate"] = N.gemm_split(A, Wp, a_relu_gate=t, **kw)
         word = N.amax_word(A.device)
-        outs[22, "out_amax"] = N.gemm_split(A, N.gemm_split_pack(W, terms=22), out_amax=word).clone()
+        outs[22, "out_amax"] = N.gemm_split(A, N.gemm_split_pack(W, terms=22), out_amax=word, **v).clone()
         outs[22, "out_amax_word"] = word.clone().view(torch.float32)
         return outs
 
-    L = N.lib()
-    assert L.sea_gemm_split_mfma_shape(-1) in (16, 32)
-    prev = L.sea_gemm_split_mfma_shape(32)
-    try:
-        o32 = all_variants()
-        assert L.sea_gemm_split_mfma_shape(16) == 32
-        o16 = all_variants()
-    finally:
-        L.sea_gemm_split_mfma_shape(prev)
+    o32 = all_variants(mfma_shape=32)
+    o16 = all_variants(mfma_shape=16)
     ref = {"plain": _ref(A, W, bias, True), "gelu": _ref(torch.nn.functional.gelu(A.double()), W),
            "addend": _ref(A, W, bias) + add.double(),
            "gelu_grad": _ref(A.double() * torch.ops.aten.gelu_backward(torch.ones_like(t), t).double(), W),
@@ -485,8 +478,8 @@ def test_prologue_with_addend_on_a_product_that_does_not_split(N, terms):
 
 @pytest.mark.parametrize("M,K,Nn", [(1000, 192, 200), (300, 96, 130), (129, 32, 21), (2048, 512, 512), (517, 1024, 384)])
 def test_pingpong_pipeline_gives_the_bits_of_the_single_stage_loop(N, M, K, Nn):
-    """sea_gemm_split_pipeline(1) (two LDS stages, one barrier per K step, staging in the MFMA shadow: csrc/gemm_split_pp.hip)
-    against pipeline 0 (csrc/gemm_split.hip): same operand split, same MFMA order per accumulator -> bit-identical outputs
+    """pipe=1 (SEA_GEMM_PIPE_PINGPONG, per call: two LDS stages, one barrier per K step, staging in the MFMA shadow: csrc/gemm_split_pp.hip)
+    against pipe=0 (csrc/gemm_split.hip): same operand split, same MFMA order per accumulator -> bit-identical outputs
     for every mode it serves (fp16 x 2, bf16 x 2, one bf16 term), every prologue, the fused epilogue, out_amax, batches,
     odd / even / single K-step counts and ragged M, N"""
     g = torch.Generator(device="cuda").manual_seed(M + K + Nn)
@@ -499,11 +492,11 @@ def test_pingpong_pipeline_gives_the_bits_of_the_single_stage_loop(N, M, K, Nn):
     A3 = torch.randn(3, M, K, generator=g, device="cuda")
     W3 = torch.randn(3, Nn, K, generator=g, device="cuda") / K ** 0.5
 
-    def all_variants():
+    def all_variants(pipe):
         outs = {}
         for terms in (22, 2, 1):
             Wp = N.gemm_split_pack(W, terms=terms)
-            kw = dict(row_amax=True) if terms == 22 else {}
+            kw = dict(row_amax=True, pipe=pipe) if terms == 22 else dict(pipe=pipe)
             outs[terms, "plain"] = N.gemm_split(A, Wp, bias=bias, relu=True, **kw)
             outs[terms, "gelu"] = N.gemm_split(A, Wp, a_gelu=True, **kw)
             outs[terms, "addend"] = N.gemm_split(A, Wp, bias=bias, addend=add, **kw)
@@ -513,21 +506,14 @@ def test_pingpong_pipeline_gives_the_bits_of_the_single_stage_loop(N, M, K, Nn):
             outs[terms, "gelu_out_pre"] = N.gemm_split(A, Wp, bias=bias, gelu_out=go, **kw)
             outs[terms, "gelu_out"] = go
             outs[terms, "gelu_grad_of"] = N.gemm_split(A, Wp, gelu_grad_of=pre, **kw)
-            outs[terms, "batch"] = N.gemm_split(A3, N.gemm_split_pack(W3, terms=terms), groups=1)
+            outs[terms, "batch"] = N.gemm_split(A3, N.gemm_split_pack(W3, terms=terms), groups=1, pipe=pipe)
         word = N.amax_word(A.device)
-        outs[22, "out_amax"] = N.gemm_split(A, N.gemm_split_pack(W, terms=22), out_amax=word).clone()
+        outs[22, "out_amax"] = N.gemm_split(A, N.gemm_split_pack(W, terms=22), out_amax=word, pipe=pipe).clone()
         outs[22, "out_amax_word"] = word.clone()
         return outs
 
-    L = N.lib()
-    assert L.sea_gemm_split_pipeline(-1) in (0, 1, 2, 3)
-    prev = L.sea_gemm_split_pipeline(0)
-    try:
-        o0 = all_variants()
-        assert L.sea_gemm_split_pipeline(1) == 0
-        o1 = all_variants()
-    finally:
-        L.sea_gemm_split_pipeline(prev)
+    o0 = all_variants(0)
+    o1 = all_variants(1)
     for key, a in o0.items():
         assert torch.equal(a, o1[key]), (key, (a.float() - o1[key].float()).abs().max().item())
     ref = _ref(A, W, bias, True)
@@ -537,8 +523,8 @@ def test_pingpong_pipeline_gives_the_bits_of_the_single_stage_loop(N, M, K, Nn):
 @pytest.mark.parametrize("G,M,K,Nn", [(3, 1024, 512, 512), (2, 700, 96, 256), (1, 300, 32, 768), (2, 2048, 160, 256), (2, 1000, 384, 384),
                                       (1, 515, 192, 1152)])
 def test_one_block_per_cu_kernels_give_the_bits_of_the_128x128_kernels(N, G, M, K, Nn):
-    """sea_gemm_split_pipeline(3) (csrc/gemm_split_big.hip: 8 waves, one block per CU; 256 x 256 tiles for the Winograd-domain
-    products, 128 x 384 tiles -- with the GELU / GELU' / gate prologues -- where N is a multiple of 384) against pipeline 0: same
+    """pipe=3 (SEA_GEMM_PIPE_BIG, per call; csrc/gemm_split_big.hip: 8 waves, one block per CU; 256 x 256 tiles for the Winograd-domain
+    products, 128 x 384 tiles -- with the GELU / GELU' / gate prologues -- where N is a multiple of 384) against pipe=0: same
     split, same MFMA order per accumulator -> the same bits, for fp16 x 2 and bf16 x 2, bias / ReLU / out_amax, ragged M (rows
     past M load zeros through the buffer descriptor) and odd / single K-step counts"""
     g = torch.Generator(device="cuda").manual_seed(M + K + Nn)
@@ -547,30 +533,68 @@ def test_one_block_per_cu_kernels_give_the_bits_of_the_128x128_kernels(N, G, M, 
     bias = torch.randn(Nn, generator=g, device="cuda")
     tt = torch.randn(G, M, K, generator=g, device="cuda")
 
-    def variants():
+    def variants(pipe):
         outs = {}
         for terms in (22, 2):
             Wp = N.gemm_split_pack(W, terms=terms)
-            outs[terms, "plain"] = N.gemm_split(A, Wp, groups=1)
-            outs[terms, "bias_relu"] = N.gemm_split(A, Wp, bias=bias, relu=True, groups=1)
+            outs[terms, "plain"] = N.gemm_split(A, Wp, groups=1, pipe=pipe)
+            outs[terms, "bias_relu"] = N.gemm_split(A, Wp, bias=bias, relu=True, groups=1, pipe=pipe)
             if Nn % 384 == 0:          # the prologues (128 x 384 tiles only)
-                outs[terms, "gelu"] = N.gemm_split(A, Wp, a_gelu=True, groups=1)
-                outs[terms, "gelu_grad"] = N.gemm_split(A, Wp, a_gelu_grad_of=tt, groups=1)
-                outs[terms, "gate"] = N.gemm_split(A, Wp, a_relu_gate=tt, groups=1)
+                outs[terms, "gelu"] = N.gemm_split(A, Wp, a_gelu=True, groups=1, pipe=pipe)
+                outs[terms, "gelu_grad"] = N.gemm_split(A, Wp, a_gelu_grad_of=tt, groups=1, pipe=pipe)
+                outs[terms, "gate"] = N.gemm_split(A, Wp, a_relu_gate=tt, groups=1, pipe=pipe)
         word = N.amax_word(A.device)
-        outs[22, "out_amax"] = N.gemm_split(A, N.gemm_split_pack(W, terms=22), out_amax=word, groups=1).clone()
+        outs[22, "out_amax"] = N.gemm_split(A, N.gemm_split_pack(W, terms=22), out_amax=word, groups=1, pipe=pipe).clone()
         outs[22, "out_amax_word"] = word.clone()
         return outs
 
-    L = N.lib()
-    prev = L.sea_gemm_split_pipeline(0)
-    try:
-        o0 = variants()
-        assert L.sea_gemm_split_pipeline(3) == 0
-        o3 = variants()
-    finally:
-        L.sea_gemm_split_pipeline(prev)
+    o0 = variants(0)
+    o3 = variants(3)
     for key, a in o0.items():
         assert torch.equal(a, o3[key]), (key, (a.float() - o3[key].float()).abs().max().item())
     ref = torch.einsum("gmk,gnk->gmn", A.double(), W.double())
     assert (o3[22, "plain"].double() - ref).abs().max().item() <= 3e-6 * ref.abs().max().item()
+
+
+def test_kernel_choice_is_per_call_and_reentrant_across_streams(N):
+    """The library keeps no switch: two streams that interleave calls on the same operands with DIFFERENT K-loop kernels
+    (pipe=0 / pipe=1 at smoke's ragged 300 x 96 by 200 x 96 product, fp16 x 2 with per-row scales; pipe=3 / pipe=0 at a
+    128 x 384-tile shape of the test above) neither disturb each other nor a call without an override in between: all
+    outputs are bitwise equal, and the graph-cache signature of the attack does not move."""
+    from semseg import attacker as At
+    model = torch.nn.Conv2d(3, 4, 1).cuda()
+    sig = At._arith_signature(model)
+    g = torch.Generator(device="cuda").manual_seed(77)
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+
+    def interleave(A, Wp, pa, pb, **kw):
+        outs = []
+        torch.cuda.synchronize()
+        for _ in range(3):
+            with torch.cuda.stream(s1):
+                outs.append(N.gemm_split(A, Wp, pipe=pa, **kw))
+            with torch.cuda.stream(s2):
+                outs.append(N.gemm_split(A, Wp, pipe=pb, **kw))
+            outs.append(N.gemm_split(A, Wp, **kw))          # no override, on the caller's stream
+        torch.cuda.synchronize()
+        return outs
+
+    A, W = torch.randn(300, 96, generator=g, device="cuda"), torch.randn(200, 96, generator=g, device="cuda")
+    outs = interleave(A, N.gemm_split_pack(W, terms=22), 0, 1, row_amax=True)
+    for o in outs[1:]:
+        assert torch.equal(outs[0], o)
+    want = A.double() @ W.double().t()
+    assert (outs[0].double() - want).abs().max() <= 3e-6 * want.abs().max()
+
+    G, M, K, Nn = 2, 1000, 384, 384
+    A3 = torch.randn(G, M, K, generator=g, device="cuda")
+    W3 = torch.randn(G, Nn, K, generator=g, device="cuda") / K ** 0.5
+    outs = interleave(A3, N.gemm_split_pack(W3, terms=22), 3, 0, groups=1)
+    for o in outs[1:]:
+        assert torch.equal(outs[0], o)
+    assert At._arith_signature(model) == sig
+    # the variant word is validated: an unknown bit is an invalid argument, not a silent default
+    Wp3, out = N.gemm_split_pack(W, terms=3), torch.empty(300, 200, device="cuda")
+    args = (N._p(A), 96, N._p(Wp3.data), N._p(out), 200, None, 0, 300, 200, 96, 3, 1, 0, 0, 0)
+    assert N.lib().sea_gemm_split(*args, 8, N._stream()) == 1
+    assert N.lib().sea_gemm_split(*args, N.gemm_variant(0, 16), N._stream()) == 0

@@ -34,9 +34,43 @@ def test_library_exports_every_declared_symbol(native):
     assert declared <= exported, declared - exported
     assert declared == set(native.EXPORTS)
     lib = native.lib()  # binds every prototype; AttributeError on ABI drift
-    assert lib.sea_abi_version() == 1
+    assert lib.sea_abi_version() == 2
     assert b"gfx950" in lib.sea_build_info()
     assert lib.sea_loss_workspace_bytes(8, 512 * 512) == (8 * 2048 + 1) * 16  # header + one record per 128-pixel tile (the smallest tile any K2 variant uses)
+
+
+def test_library_is_stateless(native):
+    """The C library keeps no mutable state: which kernel runs is a function of a call's arguments.  No setter or
+    environment-reading entry is exported, csrc/ reads the environment in ONE place (the read-only process configuration of
+    api_misc.cpp) and holds no atomics or mutable namespace-scope variables to dispatch on."""
+    out = subprocess.run(["nm", "-D", "--defined-only", native.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = set(re.findall(r" T (sea_\w+)", out))
+    gone = {"sea_gemm_split_pipeline", "sea_gemm_split_mfma_shape", "sea_attention_fwd", "sea_attention_bwd"}
+    assert not (gone & exported) and not (gone & set(native.EXPORTS))
+    csrc = os.path.join(PKG, "csrc")
+    # a definition at namespace scope that is not const / constexpr: `static int g_x = ...;`, `std::atomic<int> g{...};`
+    mutable_global = re.compile(r"^(?:static\s+)?(?!const\b|constexpr\b)(?:std::atomic\s*<[^>]*>|(?:unsigned\s+)?(?:bool|char|short|int|long|"
+                                r"float|double|size_t|u?int\d+_t)(?:\s+(?:int|long))?)\s+\w+\s*(?:=[^=;]*|\{[^;]*|\[[^\]]*\][^;(]*)?;", re.M)
+    for name in sorted(os.listdir(csrc)):
+        text = open(os.path.join(csrc, name)).read()
+        assert ("getenv" not in text) or name == "api_misc.cpp", name
+        assert "std::atomic" not in text, name
+        assert not mutable_global.findall(text), (name, mutable_global.findall(text))
+    lib = native.lib()
+    # the read-only process configuration: environment defaults of this test process, -1 for an unknown word
+    assert lib.sea_process_config(0) == int(os.environ.get("SEA_XCD_ORDER", "1")[:1])
+    assert lib.sea_process_config(1) == int(os.environ.get("SEA_UPSAMPLE_GENERAL", "0")[:1] == "1")
+    assert lib.sea_process_config(2) == -1
+    # policy lives in Python: the globals the graph-cache signature hashes, and the word they turn into
+    assert native.GEMM_PIPE in (0, 1, 2, 3) and native.GEMM_MFMA_SHAPE in (16, 32)
+    assert native.gemm_variant(2, 32) == 0 and native.gemm_variant(0, 32) == 1 and native.gemm_variant(1, 32) == 2
+    assert native.gemm_variant(3, 32) == 3 and native.gemm_variant(2, 16) == 4
+    with pytest.raises(native.SeaNativeError):
+        native.gemm_variant(4, 32)
+    header = open(os.path.join(ROOT, "include", "sea_hip.h")).read()
+    consts = {k: int(v) for k, v in re.findall(r"#define (SEA_GEMM_\w+) (\d+)u", header)}
+    assert consts == {"SEA_GEMM_VARIANT_DEFAULT": 0, "SEA_GEMM_PIPE_SINGLE": 1, "SEA_GEMM_PIPE_PINGPONG": 2, "SEA_GEMM_PIPE_BIG": 3,
+                      "SEA_GEMM_PIPE_MASK": 3, "SEA_GEMM_SHAPE16": 4}
 
 
 def test_fastdiv_magic_divides_exactly(native):

@@ -919,18 +919,13 @@ def test_dwconv7x7_nhwc_forward_and_backward_data(N, shape):
     assert torch.equal(N.dwconv7x7_nhwc(gyn, dev(wt), None, flip=2, addend=skip), gx + skip)   # `flip` is a boolean
     with pytest.raises(N.SeaNativeError):
         N.dwconv7x7_nhwc(xn, dev(wt), dev(b), addend=skip)  # bias and addend are mutually exclusive
-    # the A/B switches of the launcher (SEA_DWCONV_AB: 2 = plain block order, 4 = one row per lane, 8 = force two rows,
-    # 16 = the plain kernels instead of the software-pipelined ones of the ConvNeXt widths, 32 / 64 = their filter rows never /
-    # always through LDS)
-    import os
-    try:
-        for bits in (2, 4, 6, 8, 10, 16, 20, 24, 36, 40, 68, 72):
-            os.environ["SEA_DWCONV_AB"] = str(bits)
-            assert torch.equal(y, N.dwconv7x7_nhwc(xn, dev(wt), dev(b)))
-            assert torch.equal(gx, N.dwconv7x7_nhwc(dev(gy.permute(0, 2, 3, 1).contiguous()), dev(wt), None, flip=True))
-            assert torch.equal(N.dwconv7x7_nhwc(gyn, dev(wt), None, flip=True, addend=skip), gx + skip)
-    finally:
-        os.environ.pop("SEA_DWCONV_AB", None)
+    # the A/B switches of the launcher (the `ab` mask, per call: 2 = plain block order, 4 = one row per lane, 8 = force two
+    # rows, 16 = the plain kernels instead of the software-pipelined ones of the ConvNeXt widths, 32 / 64 = their filter rows
+    # never / always through LDS)
+    for bits in (2, 4, 6, 8, 10, 16, 20, 24, 36, 40, 68, 72):
+        assert torch.equal(y, N.dwconv7x7_nhwc(xn, dev(wt), dev(b), ab=bits))
+        assert torch.equal(gx, N.dwconv7x7_nhwc(dev(gy.permute(0, 2, 3, 1).contiguous()), dev(wt), None, flip=True, ab=bits))
+        assert torch.equal(N.dwconv7x7_nhwc(gyn, dev(wt), None, flip=True, addend=skip, ab=bits), gx + skip)
     torch.testing.assert_close(gx.cpu().permute(0, 3, 1, 2).double(), gx_ref, rtol=1e-5, atol=1e-5)
 
 
