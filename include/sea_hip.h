@@ -47,7 +47,8 @@ extern "C" {
 #define SEA_LAYOUT_NHWC 1
 
 /* library / build identification */
-int sea_abi_version(void);   /* 2: kernel variants are arguments (sea_gemm_split*, sea_dwconv7x7_nhwc*, ...), no setters */
+int sea_abi_version(void);   /* 3: kernel variants are arguments (sea_gemm_split*, sea_dwconv7x7_nhwc*, ...), no setters;
+                              *    one replayable form of K1 / K7 (radius and run length in device memory) */
 const char* sea_build_info(void);
 /* The process configuration: two A/B switches that dozens of launchers consult, read from the environment ONCE at first use
  * and immutable afterwards; every other choice is an argument of the call it concerns.  Read-only; -1 for an unknown word.
@@ -197,29 +198,23 @@ int sea_apgd_track(const float* loss_sum, const float* track_sum, const int32_t*
                    int early_stop, int init, int32_t* acc_cnt, float* acc, float* loss_best,
                    float* loss_best_last, float* reduced_last, float* step, float* loss_steps,
                    uint8_t* flags, int32_t* done, const void* loss_workspace, void* stream);
-/* Replayable forms for a caller that captures one loop iteration in a HIP graph (every per-iteration scalar in device
- * memory, fixed buffer addresses):
- *   sea_apgd_linf_step_graph: K1 IN PLACE (x_old <- x_adv, x_adv <- new iterate); a = 1 when *iter_dev == 0, else 0.75.
- *   sea_apgd_track_graph:     K7 (init = 0) with iter = *iter_dev and check_k = check_table[iter] (n_iter int32 entries,
- *                             0 = no checkpoint); advances *iter_dev by one at its end. */
+/* Replayable forms of K1 / K7: what the attack loop runs every iteration, executed eagerly or recorded once in a HIP graph
+ * and replayed.  Everything run-specific is a word in device memory and the buffers keep their addresses, so nothing is left
+ * in the launch arguments: ONE recorded pair serves every stage, loss and batch of an evaluation (reference
+ * semseg/attacker.py:691-728: three apgd_train calls per attack with eps 2e / 1.5e / e and 0.3n / 0.3n / 0.4n iterations;
+ * tools/infer.py:338-370: three attacks per batch).
+ *   sea_apgd_linf_step_graph: K1 IN PLACE (x_old <- x_adv, x_adv <- new iterate) with eps = *eps_dev (one float);
+ *                             a = 1 when *iter_dev == 0, else 0.75.
+ *   sea_apgd_track_graph:     K7 (init = 0) with iter = *iter_dev, n_iter = *n_iter_dev (one int32) and
+ *                             check_k = check_table[iter] (0 = no checkpoint); advances *iter_dev by one at its end.
+ *                             check_table and loss_steps must be sized for the longest run replayed. */
 int sea_apgd_linf_step_graph(const float* x, float* x_adv, float* x_old, const float* grad, const float* step_b,
-                             float eps, const int32_t* iter_dev, int B, int64_t n_per_img, void* stream);
+                             const float* eps_dev, const int32_t* iter_dev, int B, int64_t n_per_img, void* stream);
 int sea_apgd_track_graph(const float* loss_sum, const float* track_sum, const int32_t* n_correct,
                          const int32_t* n_ignored, int B, int64_t HW, int32_t* iter_dev, const int32_t* check_table,
-                         int n_iter, int early_stop, int32_t* acc_cnt, float* acc, float* loss_best,
+                         const int32_t* n_iter_dev, int early_stop, int32_t* acc_cnt, float* acc, float* loss_best,
                          float* loss_best_last, float* reduced_last, float* step, float* loss_steps, uint8_t* flags,
                          int32_t* done, const void* loss_workspace, void* stream);
-/* The same two with the run's radius (one float) and length (one int32) in device memory as well: nothing run-specific is
- * left in the launch arguments, so ONE captured graph pair serves every stage, loss and batch of an evaluation (reference
- * semseg/attacker.py:691-728: three apgd_train calls per attack with eps 2e / 1.5e / e and 0.3n / 0.3n / 0.4n iterations;
- * tools/infer.py:338-370: three attacks per batch).  check_table and loss_steps must be sized for the longest run replayed. */
-int sea_apgd_linf_step_graph_dev(const float* x, float* x_adv, float* x_old, const float* grad, const float* step_b,
-                                 const float* eps_dev, const int32_t* iter_dev, int B, int64_t n_per_img, void* stream);
-int sea_apgd_track_graph_dev(const float* loss_sum, const float* track_sum, const int32_t* n_correct,
-                             const int32_t* n_ignored, int B, int64_t HW, int32_t* iter_dev, const int32_t* check_table,
-                             const int32_t* n_iter_dev, int early_stop, int32_t* acc_cnt, float* acc, float* loss_best,
-                             float* loss_best_last, float* reduced_last, float* step, float* loss_steps, uint8_t* flags,
-                             int32_t* done, const void* loss_workspace, void* stream);
 int sea_select_copy(const uint8_t* flags, float* x_adv, float* grad, float* x_best,
                     float* grad_best, float* x_best_adv, const void* pred, void* pred_best,
                     int pred_bytes, int B, int64_t n_per_img, int64_t HW, void* stream);

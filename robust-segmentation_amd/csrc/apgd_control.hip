@@ -22,12 +22,12 @@ __global__ __launch_bounds__(1024) void apgd_track_kernel(
     float* __restrict__ loss_best_last, float* __restrict__ reduced_last, float* __restrict__ step,
     float* __restrict__ loss_steps, uint8_t* __restrict__ flags, int32_t* __restrict__ done,
     const LossRecord* __restrict__ records, int32_t* __restrict__ iter_dev, const int32_t* __restrict__ check_table,
-    const int32_t* __restrict__ n_iter_dev = nullptr) {
-  // replayable form (HIP-graph mode): the loop index lives in *iter_dev, the checkpoint window of iteration i in
-  // check_table[i]; the counter is advanced at the very end, after every use (K1 of this step has read it already).
-  // With n_iter_dev the run length is device state too: one captured graph serves stages of any length.
-  if (n_iter_dev != nullptr) n_iter = *n_iter_dev;
+    const int32_t* __restrict__ n_iter_dev) {
+  // replayable form (the one the attack loop runs, eagerly or from a HIP graph): the loop index lives in *iter_dev, the run
+  // length in *n_iter_dev and the checkpoint window of iteration i in check_table[i], so one captured launch serves runs of
+  // any length; the counter is advanced at the very end, after every use (K1 of this step has read it already).
   if (iter_dev != nullptr) {
+    n_iter = *n_iter_dev;
     iter = *iter_dev;
     iter = iter < 0 ? 0 : (iter >= n_iter ? n_iter - 1 : iter);
     check_k = check_table[iter];
@@ -253,49 +253,26 @@ extern "C" int sea_apgd_track(const float* loss_sum, const float* track_sum, con
                      track_sum, n_correct, n_ignored, B, HW, iter, n_iter, check_k, early_stop, init, acc_cnt, acc, loss_best,
                      loss_best_last, reduced_last, step, loss_steps, flags, done,
                      (track_sum && n_correct) ? (const LossRecord*)nullptr : (const LossRecord*)loss_workspace,
-                     (int32_t*)nullptr, (const int32_t*)nullptr);
+                     (int32_t*)nullptr, (const int32_t*)nullptr, (const int32_t*)nullptr);
   SEA_RETURN_LAST();
 }
 
-static int track_graph_impl(const float* loss_sum, const float* track_sum, const int32_t* n_correct, const int32_t* n_ignored, int B,
-                            int64_t HW, int32_t* iter_dev, const int32_t* check_table, int n_iter, const int32_t* n_iter_dev,
-                            int early_stop, int32_t* acc_cnt, float* acc, float* loss_best, float* loss_best_last,
-                            float* reduced_last, float* step, float* loss_steps, uint8_t* flags, int32_t* done,
-                            const void* loss_workspace, void* stream) {
+// check_table and loss_steps are sized for the longest run the caller will replay
+extern "C" int sea_apgd_track_graph(const float* loss_sum, const float* track_sum, const int32_t* n_correct,
+                                    const int32_t* n_ignored, int B, int64_t HW, int32_t* iter_dev,
+                                    const int32_t* check_table, const int32_t* n_iter_dev, int early_stop, int32_t* acc_cnt,
+                                    float* acc, float* loss_best, float* loss_best_last, float* reduced_last, float* step,
+                                    float* loss_steps, uint8_t* flags, int32_t* done, const void* loss_workspace,
+                                    void* stream) {
   SEA_CHECK_ARG(acc_cnt && acc && loss_best && loss_best_last && reduced_last && step && flags && done && B > 0 &&
-                HW > 0 && iter_dev && check_table && n_ignored && loss_steps && n_iter > 0);
+                HW > 0 && iter_dev && check_table && n_iter_dev && n_ignored && loss_steps);
   SEA_CHECK_ARG((track_sum && n_correct) || (loss_workspace && B <= 1024));
   hipLaunchKernelGGL(apgd_track_kernel, dim3(1), dim3(track_block(track_sum, n_correct)), 0, (hipStream_t)stream, loss_sum,
-                     track_sum, n_correct, n_ignored, B, HW, 0, n_iter, 0, early_stop, 0, acc_cnt, acc, loss_best, loss_best_last, reduced_last,
-                     step, loss_steps, flags, done,
+                     track_sum, n_correct, n_ignored, B, HW, 0, 0, 0, early_stop, 0, acc_cnt, acc, loss_best, loss_best_last,
+                     reduced_last, step, loss_steps, flags, done,
                      (track_sum && n_correct) ? (const LossRecord*)nullptr : (const LossRecord*)loss_workspace, iter_dev,
                      check_table, n_iter_dev);
   SEA_RETURN_LAST();
-}
-
-extern "C" int sea_apgd_track_graph(const float* loss_sum, const float* track_sum, const int32_t* n_correct,
-                                    const int32_t* n_ignored, int B, int64_t HW, int32_t* iter_dev,
-                                    const int32_t* check_table, int n_iter, int early_stop, int32_t* acc_cnt, float* acc,
-                                    float* loss_best, float* loss_best_last, float* reduced_last, float* step,
-                                    float* loss_steps, uint8_t* flags, int32_t* done, const void* loss_workspace,
-                                    void* stream) {
-  return track_graph_impl(loss_sum, track_sum, n_correct, n_ignored, B, HW, iter_dev, check_table, n_iter, nullptr, early_stop,
-                          acc_cnt, acc, loss_best, loss_best_last, reduced_last, step, loss_steps, flags, done, loss_workspace,
-                          stream);
-}
-
-// the same with the run length read from device memory (check_table and loss_steps sized for the longest run the caller
-// will replay): a captured graph then serves runs of any length
-extern "C" int sea_apgd_track_graph_dev(const float* loss_sum, const float* track_sum, const int32_t* n_correct,
-                                        const int32_t* n_ignored, int B, int64_t HW, int32_t* iter_dev,
-                                        const int32_t* check_table, const int32_t* n_iter_dev, int early_stop, int32_t* acc_cnt,
-                                        float* acc, float* loss_best, float* loss_best_last, float* reduced_last, float* step,
-                                        float* loss_steps, uint8_t* flags, int32_t* done, const void* loss_workspace,
-                                        void* stream) {
-  SEA_CHECK_ARG(n_iter_dev != nullptr);
-  return track_graph_impl(loss_sum, track_sum, n_correct, n_ignored, B, HW, iter_dev, check_table, 1, n_iter_dev, early_stop,
-                          acc_cnt, acc, loss_best, loss_best_last, reduced_last, step, loss_steps, flags, done, loss_workspace,
-                          stream);
 }
 
 extern "C" int sea_select_copy(const uint8_t* flags, float* x_adv, float* grad, float* x_best, float* grad_best,

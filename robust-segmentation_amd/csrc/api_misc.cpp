@@ -7,7 +7,7 @@
 #define SEA_BUILD_STAMP "unknown"
 #endif
 
-extern "C" int sea_abi_version(void) { return 2; }
+extern "C" int sea_abi_version(void) { return 3; }
 extern "C" const char* sea_build_info(void) { return "libsea_hip gfx950 " SEA_BUILD_STAMP; }
 
 namespace sea {

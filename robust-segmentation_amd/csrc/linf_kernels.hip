@@ -79,17 +79,18 @@ __global__ __launch_bounds__(256) void apgd_linf_step_v1(const float* __restrict
     out[base + i] = apgd_elem(x[base + i], xadv[base + i], xold[base + i], grad[base + i], st, eps, a, oma);
 }
 
-// Replayable form of K1 (HIP-graph mode of the attack loop): every per-iteration scalar comes from device memory and
-// the iterate buffers keep their addresses.  *iter_dev is the loop index i (a = 1 for i = 0, else 0.75; K7 advances it);
-// the update is IN PLACE: x_old <- x_adv (the reference's `x_adv_old = x_adv.clone()`, attacker.py:390) and
-// x_adv <- new iterate, element by element (each element is read before it is written, by the same lane).
+// Replayable form of K1, the one the attack loop runs (executed eagerly or recorded in a HIP graph): the radius and the
+// loop index come from device memory and the iterate buffers keep their addresses, so nothing run-specific is left in the
+// launch arguments.  *iter_dev is the loop index i (a = 1 for i = 0, else 0.75; K7 advances it); the update is IN PLACE:
+// x_old <- x_adv (the reference's `x_adv_old = x_adv.clone()`, attacker.py:390) and x_adv <- new iterate, element by element
+// (each element is read before it is written, by the same lane).
 __global__ __launch_bounds__(256) void apgd_linf_step_inplace_v4(const f4* __restrict__ x, f4* __restrict__ xadv,
                                                                  f4* __restrict__ xold, const f4* __restrict__ grad,
-                                                                 const float* __restrict__ step_b, float eps_val,
-                                                                 const int32_t* __restrict__ iter_dev,
-                                                                 int64_t n4_per_img, const float* __restrict__ eps_dev) {
+                                                                 const float* __restrict__ step_b,
+                                                                 const float* __restrict__ eps_dev,
+                                                                 const int32_t* __restrict__ iter_dev, int64_t n4_per_img) {
   const int b = blockIdx.y;
-  const float eps = eps_dev ? *eps_dev : eps_val;   // (the radius as run-invariant device state: one captured graph serves every stage)
+  const float eps = *eps_dev;
   const float st = step_b[b];
   const bool first = *iter_dev <= 0;
   const float a = first ? 1.0f : 0.75f;
@@ -106,11 +107,11 @@ __global__ __launch_bounds__(256) void apgd_linf_step_inplace_v4(const f4* __res
 // not 16-byte aligned): one float per lane and trip
 __global__ __launch_bounds__(256) void apgd_linf_step_inplace_v1(const float* __restrict__ x, float* __restrict__ xadv,
                                                                  float* __restrict__ xold, const float* __restrict__ grad,
-                                                                 const float* __restrict__ step_b, float eps_val,
-                                                                 const int32_t* __restrict__ iter_dev, int64_t n_per_img,
-                                                                 const float* __restrict__ eps_dev) {
+                                                                 const float* __restrict__ step_b,
+                                                                 const float* __restrict__ eps_dev,
+                                                                 const int32_t* __restrict__ iter_dev, int64_t n_per_img) {
   const int b = blockIdx.y;
-  const float eps = eps_dev ? *eps_dev : eps_val;
+  const float eps = *eps_dev;
   const float st = step_b[b];
   const bool first = *iter_dev <= 0;
   const float a = first ? 1.0f : 0.75f;
@@ -257,38 +258,26 @@ extern "C" int sea_apgd_linf_step(const float* x, const float* x_adv, const floa
   SEA_RETURN_LAST();
 }
 
-static int linf_step_graph_impl(const float* x, float* x_adv, float* x_old, const float* grad, const float* step_b, float eps,
-                                const float* eps_dev, const int32_t* iter_dev, int B, int64_t n_per_img, void* stream) {
-  SEA_CHECK_ARG(x && x_adv && x_old && grad && step_b && iter_dev && B > 0 && n_per_img > 0 && B <= 65535);
+// the radius is one float in device memory: a captured launch serves runs of any radius
+extern "C" int sea_apgd_linf_step_graph(const float* x, float* x_adv, float* x_old, const float* grad,
+                                        const float* step_b, const float* eps_dev, const int32_t* iter_dev, int B,
+                                        int64_t n_per_img, void* stream) {
+  SEA_CHECK_ARG(x && x_adv && x_old && grad && step_b && eps_dev && iter_dev && B > 0 && n_per_img > 0 && B <= 65535);
   int cap = kMaxGridX / B;
   if (cap < 1) cap = 1;
   if ((n_per_img % 4) != 0 || !(aligned16(x) && aligned16(x_adv) && aligned16(x_old) && aligned16(grad))) {
     int gx1 = grid_for(n_per_img, 256);
     if (gx1 > cap) gx1 = cap;
     hipLaunchKernelGGL(apgd_linf_step_inplace_v1, dim3(gx1, B), dim3(256), 0, (hipStream_t)stream, x, x_adv, x_old, grad, step_b,
-                       eps, iter_dev, n_per_img, eps_dev);
+                       eps_dev, iter_dev, n_per_img);
     SEA_RETURN_LAST();
   }
   const int64_t n4 = n_per_img / 4;
   int gx = grid_for(n4, 256);
   if (gx > cap) gx = cap;
   hipLaunchKernelGGL(apgd_linf_step_inplace_v4, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, (const f4*)x, (f4*)x_adv,
-                     (f4*)x_old, (const f4*)grad, step_b, eps, iter_dev, n4, eps_dev);
+                     (f4*)x_old, (const f4*)grad, step_b, eps_dev, iter_dev, n4);
   SEA_RETURN_LAST();
-}
-
-extern "C" int sea_apgd_linf_step_graph(const float* x, float* x_adv, float* x_old, const float* grad,
-                                        const float* step_b, float eps, const int32_t* iter_dev, int B,
-                                        int64_t n_per_img, void* stream) {
-  return linf_step_graph_impl(x, x_adv, x_old, grad, step_b, eps, nullptr, iter_dev, B, n_per_img, stream);
-}
-
-// the same with the radius read from device memory (one float): a captured graph then serves runs of any radius
-extern "C" int sea_apgd_linf_step_graph_dev(const float* x, float* x_adv, float* x_old, const float* grad,
-                                            const float* step_b, const float* eps_dev, const int32_t* iter_dev, int B,
-                                            int64_t n_per_img, void* stream) {
-  SEA_CHECK_ARG(eps_dev != nullptr);
-  return linf_step_graph_impl(x, x_adv, x_old, grad, step_b, 0.f, eps_dev, iter_dev, B, n_per_img, stream);
 }
 
 template <int OP>

@@ -44,12 +44,9 @@ _SIGS = {
     "sea_confusion": (_i, [_vp, _i, _vp, _i, _i64, _i, _vp, _vp]),
     "sea_apgd_track": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                             _vp, _vp, _vp, _vp]),
-    "sea_apgd_linf_step_graph": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i64, _vp]),
-    "sea_apgd_track_graph": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+    "sea_apgd_linf_step_graph": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp]),
+    "sea_apgd_track_graph": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                   _vp, _vp, _vp]),
-    "sea_apgd_linf_step_graph_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp]),
-    "sea_apgd_track_graph_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                      _vp, _vp, _vp]),
     "sea_select_copy": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i64, _vp]),
     "sea_count_ignored": (_i, [_vp, _i, _i, _i64, _vp, _vp]),
     "sea_worst_miou_greedy": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
@@ -689,36 +686,25 @@ def apgd_track(stats, n_ignored, HW: int, it: int, n_iter: int, check_k: int, ea
 
 
 def apgd_linf_step_graph(x, x_adv, x_old, grad, step_b, eps, iter_dev):
-    """K1 in place with the loop index read from device memory (HIP-graph mode): x_old <- x_adv, x_adv <- new.
-    ``eps``: a Python float, or ONE float32 in device memory (the radius as device state too)."""
+    """Replayable K1, in place: x_old <- x_adv, x_adv <- new.  The radius ``eps`` (ONE float32) and the loop index
+    ``iter_dev`` are read from device memory."""
     _dev(x, x_adv, x_old, grad, step_b, iter_dev)
     for t in (x, x_adv, x_old, grad):
         if t.dtype != torch.float32 or not t.is_contiguous():
             raise SeaNativeError("apgd_linf_step_graph: contiguous float32 buffers expected")
-    if torch.is_tensor(eps):
-        if eps.dtype != torch.float32 or eps.numel() != 1 or eps.device != x.device:
-            raise SeaNativeError("apgd_linf_step_graph: a tensor eps must be one float32 on x's device")
-        _check(lib().sea_apgd_linf_step_graph_dev(_p(x), _p(x_adv), _p(x_old), _p(grad), _p(_f32c(step_b)), _p(eps), _p(iter_dev),
-                                                  x.shape[0], x[0].numel(), _stream()), "sea_apgd_linf_step_graph_dev")
-        return
-    _check(lib().sea_apgd_linf_step_graph(_p(x), _p(x_adv), _p(x_old), _p(grad), _p(_f32c(step_b)), eps, _p(iter_dev),
+    if not torch.is_tensor(eps) or eps.dtype != torch.float32 or eps.numel() != 1 or eps.device != x.device:
+        raise SeaNativeError("apgd_linf_step_graph: eps must be one float32 on x's device")
+    _check(lib().sea_apgd_linf_step_graph(_p(x), _p(x_adv), _p(x_old), _p(grad), _p(_f32c(step_b)), _p(eps), _p(iter_dev),
                                           x.shape[0], x[0].numel(), _stream()), "sea_apgd_linf_step_graph")
 
 
 def apgd_track_graph(stats, n_ignored, HW: int, iter_dev, check_table, n_iter, early_stop: bool, st):
-    """K7 with the loop index and the checkpoint schedule in device memory; advances ``iter_dev``.  ``n_iter``: an int, or ONE
-    int32 in device memory (``check_table`` and ``st.loss_steps`` then sized for the longest run replayed)."""
-    if torch.is_tensor(n_iter):
-        if n_iter.dtype != torch.int32 or n_iter.numel() != 1:
-            raise SeaNativeError("apgd_track_graph: a tensor n_iter must be one int32")
-        _check(lib().sea_apgd_track_graph_dev(_p(stats["loss_sum"]), _p(stats["track_sum"]), _p(stats["n_correct"]),
-                                              _p(n_ignored), st.B, HW, _p(iter_dev), _p(check_table), _p(n_iter), int(early_stop),
-                                              _p(st.acc_cnt), _p(st.acc), _p(st.loss_best), _p(st.loss_best_last),
-                                              _p(st.reduced_last), _p(st.step), _p(st.loss_steps), _p(st.flags), _p(st.done),
-                                              _p(stats.get("workspace")), _stream()), "sea_apgd_track_graph_dev")
-        return
+    """Replayable K7: the loop index, the run length ``n_iter`` (ONE int32) and the checkpoint schedule are read from device
+    memory (``check_table`` and ``st.loss_steps`` sized for the longest run replayed); advances ``iter_dev``."""
+    if not torch.is_tensor(n_iter) or n_iter.dtype != torch.int32 or n_iter.numel() != 1:
+        raise SeaNativeError("apgd_track_graph: n_iter must be one int32 in device memory")
     _check(lib().sea_apgd_track_graph(_p(stats["loss_sum"]), _p(stats["track_sum"]), _p(stats["n_correct"]),
-                                      _p(n_ignored), st.B, HW, _p(iter_dev), _p(check_table), n_iter, int(early_stop),
+                                      _p(n_ignored), st.B, HW, _p(iter_dev), _p(check_table), _p(n_iter), int(early_stop),
                                       _p(st.acc_cnt), _p(st.acc), _p(st.loss_best), _p(st.loss_best_last),
                                       _p(st.reduced_last), _p(st.step), _p(st.loss_steps), _p(st.flags), _p(st.done),
                                       _p(stats.get("workspace")), _stream()), "sea_apgd_track_graph")

@@ -288,7 +288,7 @@ FUSE_UPSAMPLE_MIN_CLASSES = 96
 # A/B switch (env SEA_K2U_POW2=0): K2u's general gather kernel at the factors 4 and 16 too (the one place it is read)
 K2U_POW2 = os.environ.get("SEA_K2U_POW2", "1")[:1] != "0"
 
-# HIP-graph replay of the middle iterations of an APGD run (see ApgdRun._capture).  SEA_HIP_GRAPH=0 disables it.
+# HIP-graph replay of the middle iterations of an APGD run (see ApgdRun._capture).  SEA_HIP_GRAPH=0 executes every one.
 USE_HIP_GRAPH = os.environ.get("SEA_HIP_GRAPH", "1") != "0"
 GRAPH_MIN_ITER = 12
 
@@ -312,12 +312,13 @@ def _capture_stream(device):
 # ---- one owner for a run's device buffers and its captured graph pair -------------------------------------------------------
 # SEA runs nine apgd_train calls per batch (three losses x three stages, reference attacker.py:691-728 and
 # tools/infer.py:338-370).  Nothing distinguishes them for the captured graphs except the radius, the run length (with its
-# checkpoint table) and the contents of the buffers: all of that is DEVICE STATE here (sea_apgd_linf_step_graph_dev /
-# sea_apgd_track_graph_dev read eps and n_iter from memory) and the loss is chosen by the eager K2 launch between the two
-# graphs.  So every run works in the buffers of exactly ONE owner (`_RunBuffers`), which also holds the pair that addresses
-# them: the caller's tensors are copied in and never written, the results are copied out.  An owner cached on the model
-# (`_graph_slot`) outlives its run: the pair is captured ONCE per (model weights, batch shape, classes, K2 or K2u) and replayed
-# by every stage, loss and batch of equal shape; round 4 captured nine pairs per batch (3.7 % of the protocol's wall time).
+# checkpoint table) and the contents of the buffers: all of that is DEVICE STATE here (the replayable K1 / K7, which every
+# iteration runs, read eps, n_iter and the loop index from memory and update the iterate in place in `x_adv` / `x_old`) and
+# the loss is chosen by the eager K2 launch between the two graphs.  So every run works in the buffers of exactly ONE owner
+# (`_RunBuffers`), which also holds the pair that addresses them: the caller's tensors are copied in and never written, the
+# results are copied out.  An owner cached on the model (`_graph_slot`) outlives its run: the pair is captured ONCE per (model
+# weights, batch shape, classes, K2 or K2u) and replayed by every stage, loss and batch of equal shape; round 4 captured nine
+# pairs per batch (3.7 % of the protocol's wall time).
 # A run that gets no cached owner (eager loop, SEA_GRAPH_CACHE=0, a nested run, weights that moved between two runs, L2)
 # constructs a private one sized for its own length, starts without a pair and frees pair and activation pool on release.
 GRAPH_CACHE = os.environ.get("SEA_GRAPH_CACHE", "1") != "0"
@@ -333,7 +334,7 @@ class _RunBuffers:
         dev, B = x.device, x.shape[0]
         self.weights_key, self.cap_iter = weights_key, cap_iter
         new = lambda: torch.empty_like(x, memory_format=torch.contiguous_format)  # noqa: E731
-        self.x, self.bufs, self.grad = new(), [new(), new(), new()], new()
+        self.x, self.x_adv, self.x_old, self.grad = new(), new(), new(), new()
         self.x_best, self.x_best_adv, self.grad_best = new(), new(), new()
         pred_dtype = torch.uint8 if num_classes <= 255 else torch.int16
         self.pred = torch.empty(B, x.shape[-2], x.shape[-1], dtype=pred_dtype, device=dev)
@@ -365,6 +366,7 @@ class _RunBuffers:
         for k, v in cps.items():
             tab[k] = v
         self.cp_dev.copy_(tab)
+        self.it_dev.zero_()         # from here on the loop index is device state only: K1 reads it, K7 advances it
         self.eps_dev.fill_(eps)
         self.niter_dev.fill_(max(n_iter, 1))
 
@@ -503,7 +505,7 @@ class ApgdRun:
                  fuse_upsample=None, norm="Linf"):
         self.model = model
         self.norm = norm               # "Linf" (K1) or "L2" (K1': four streaming passes, reference lines 412-436)
-        self._l2_ws = None
+        self._l2_ws = self._l2_next = None
         # fuse the model's final bilinear upsample into the loss kernel when the model offers the hook
         if fuse_upsample is None:
             fuse_upsample = FUSE_UPSAMPLE
@@ -543,11 +545,9 @@ class ApgdRun:
         own = _graph_slot(model, x, num_classes, n_iter, self.fused) if (self.use_graph and x.is_contiguous()) else None
         self._private = own is None
         self.own = own = _RunBuffers(x, num_classes, max(n_iter, 1)) if own is None else own
-        # A run that finds the pair already captured replays it from iteration 0 (the in-place K1 takes a = 1 there from the
-        # device-side loop index): its iterate starts in the buffer the pair addresses as x_adv, bufs[1] -- where the two
-        # eager iterations of the capturing run (library warm-up on the capture stream) had rotated it to
-        self._first_graph_step, k = (0, 1) if own.graphs is not None else (2, 0)
-        self.x_adv, self.x_old, self.x_next = (own.bufs[(k + j) % 3] for j in range(3))
+        # a run that finds the pair already captured replays it from iteration 0
+        self._first_graph_step = 0 if own.graphs is not None else 2
+        self.x_adv, self.x_old = own.x_adv, own.x_old
         own.x.copy_(x)
         self.x_adv.copy_(x_start)
         N.count_ignored(self.yc, out=own.n_ignored)
@@ -608,37 +608,49 @@ class ApgdRun:
                 return
         self._step_eager(i)
 
-    def _step_eager(self, i: int):
+    # ---- one iteration = front, _loss, back: each written once, executed (eager) or recorded and replayed (HIP-graph mode) ----
+    def _front(self, i: int, want_grad: bool, k1: bool = True):
+        """gradient step (reference lines 389-456), in place, and the model forward on the new iterate"""
         o = self.own
-        # ---- gradient step (reference lines 389-456): K1, then rotate the three iterate buffers
-        a = 0.75 if i > 0 else 1.0
-        if self.norm == "L2":
-            if self._l2_ws is None:
-                self._l2_ws = torch.empty(N.lib().sea_apgd_l2_workspace_bytes(self.B) // 8, dtype=torch.float64, device=o.x.device)
-            N.apgd_l2_step(o.x, self.x_adv, self.x_old, o.grad, o.st.step, self.eps, a, out=self.x_next, workspace=self._l2_ws)
-        else:
-            N.apgd_linf_step(o.x, self.x_adv, self.x_old, o.grad, o.st.step, self.eps, a, out=self.x_next)
-        self.x_old, self.x_adv, self.x_next = self.x_adv, self.x_next, self.x_old
-        # ---- model forward, fused loss/grad/track/acc/argmax (K2), model input-gradient
-        want = i < self.n_iter - 1  # the reference skips the last backward (line 467)
-        x_in, logits = _forward_logits(self.model, self.x_adv, want, self.fused)
-        r = self._loss(logits, want)
-        if want:
+        if k1 and self.norm == "Linf":
+            N.apgd_linf_step_graph(o.x, self.x_adv, self.x_old, o.grad, o.st.step, o.eps_dev, o.it_dev)
+        elif k1:
+            self._l2_step(i)
+        return _forward_logits(self.model, self.x_adv, want_grad, self.fused)
+
+    def _back(self, x_in, logits, r, want_grad: bool = True):
+        """model input-gradient, then the bookkeeping on the device (K7 decisions, K4 copies)"""
+        o = self.own
+        if want_grad:
             o.grad.copy_(_input_grad(logits, x_in, r["dlogits"]))   # the gradient buffer keeps its address (K1 / K4 read it)
-        del logits
-        # ---- bookkeeping on the device (K7 decisions, K4 copies)
-        N.apgd_track(r, o.n_ignored, self.HW, i, self.n_iter, self.cps.get(i, 0), self.early_stop, False, o.st)
+        N.apgd_track_graph(r, o.n_ignored, self.HW, o.it_dev, o.cp_dev, o.niter_dev, self.early_stop, o.st)
         self._select()
+
+    def _step_eager(self, i: int, k1: bool = True):
+        want = i < self.n_iter - 1  # the reference skips the last backward (line 467)
+        x_in, logits = self._front(i, want, k1)
+        self._back(x_in, logits, self._loss(logits, want), want)
+
+    def _l2_step(self, i: int):
+        """K1' re-reads x_adv and x_old in four passes: it writes a third buffer and the three rotate (L2 never captures)"""
+        o = self.own
+        if self._l2_ws is None:
+            self._l2_ws = torch.empty(N.lib().sea_apgd_l2_workspace_bytes(self.B) // 8, dtype=torch.float64, device=o.x.device)
+            self._l2_next = torch.empty_like(o.x)
+        N.apgd_l2_step(o.x, self.x_adv, self.x_old, o.grad, o.st.step, self.eps, 0.75 if i > 0 else 1.0, out=self._l2_next,
+                       workspace=self._l2_ws)
+        self.x_old, self.x_adv, self._l2_next = self.x_adv, self._l2_next, self.x_old
 
     # ---- HIP-graph mode ----------------------------------------------------------------------------------------
     # An iteration is ~360 kernel launches that the host needs 9-14 ms to enqueue (ConvNeXt-T, B=8) for 22 ms of GPU
     # work: hidden on one GPU, not with 8 ranks on one host or a faster model side.  With `use_graph` the middle
-    # iterations (2 <= i < n_iter - 1) are replays of TWO captured graphs around the one eager K2 launch:
-    #     graph A = K1 (in place, `a` from the device-side loop index) + model forward
-    #     K2      = eager (so a caller can still bracket it with events; bench.py does)
-    #     graph B = input-gradient backward + K7 (loop index / checkpoint window from device memory) + K4
-    # Iterations 0 and 1 run eagerly (library warm-up on the capture stream), the last one too (no backward there).
-    # Same kernels, same arithmetic, same order: the outputs are bitwise those of the eager loop (tested).
+    # iterations (_first_graph_step <= i < n_iter - 1) replay the two recorded pieces around the one eager K2 launch:
+    #     graph A = front (K1 in place + model forward)
+    #     K2      = _loss, eager (so a caller can still bracket it with events; bench.py does)
+    #     graph B = back (input-gradient backward + K7 + K4)
+    # A run that has to capture executes iterations 0 and 1 first (library warm-up, iteration 1 on the capture stream); the
+    # last iteration is always executed (no backward there).  Same calls, same kernels, same order in both modes: the
+    # outputs are bitwise those of the eager loop (tested).
     def _graph_failed(self, exc):
         """A model whose forward / backward cannot be captured (a host sync such as .item(), a library that allocates or
         JIT-compiles on first use of a shape, ...) keeps working: the run continues with the eager loop, which is the same
@@ -654,15 +666,13 @@ class ApgdRun:
         torch.cuda.synchronize()
 
     def _capture(self, i: int):
-        """captures the two graphs AND performs iteration i; falls back to the eager loop when a capture fails"""
+        """records front and back AND performs iteration i by replaying them; falls back to the eager loop when a capture fails"""
         o = self.own
         self._caller_stream = torch.cuda.current_stream()
-        o.it_dev.fill_(i)          # radius, run length, checkpoint table: device words too (set by o.reset)
         ga, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         try:
             with torch.cuda.graph(ga, stream=self._gs):
-                N.apgd_linf_step_graph(o.x, self.x_adv, self.x_old, o.grad, o.st.step, o.eps_dev, o.it_dev)
-                g_xin, g_logits = _forward_logits(self.model, self.x_adv, True, self.fused)
+                g_xin, g_logits = self._front(i, True)
         except Exception as exc:   # nothing of iteration i has run yet (a capture executes nothing)
             self._graph_failed(exc)
             return self._step_eager(i)
@@ -670,21 +680,13 @@ class ApgdRun:
         r = self._loss(g_logits, True)                # eager, and it defines the (persistent) K2 output buffers
         try:
             with torch.cuda.graph(gb, pool=ga.pool(), stream=self._gs):
-                o.grad.copy_(_input_grad(g_logits, g_xin, r["dlogits"]))
-                N.apgd_track_graph(r, o.n_ignored, self.HW, o.it_dev, o.cp_dev, o.niter_dev, self.early_stop, o.st)
-                self._select()
+                self._back(g_xin, g_logits, r)
         except Exception as exc:   # K1 of iteration i is done (graph A replayed, in place): finish the iteration eagerly.
             # The failed capture has consumed the autograd graph of graph A's forward, so the forward is run again, on the
             # updated iterate (same kernels, same bits)
             self._graph_failed(exc)
             del g_xin, g_logits
-            x_in, logits = _forward_logits(self.model, self.x_adv, True, self.fused)
-            r = self._loss(logits, True)
-            o.grad.copy_(_input_grad(logits, x_in, r["dlogits"]))
-            del logits
-            N.apgd_track(r, o.n_ignored, self.HW, i, self.n_iter, self.cps.get(i, 0), self.early_stop, False, o.st)
-            self._select()
-            return
+            return self._step_eager(i, k1=False)
         gb.replay()
         o.keep_graphs((ga, gb), self._graph_sig(), g_xin, g_logits)
 
@@ -695,11 +697,8 @@ class ApgdRun:
 
     def _step_graph(self, i: int):
         o = self.own
-        if o.graphs is not None and i == self._first_graph_step:
-            if o.sig != self._graph_sig():                # (a verbose run after a silent one: capture again)
-                o.drop_graphs()
-            else:
-                o.it_dev.fill_(i)                         # the loop index of the pair's first replay in THIS run
+        if o.graphs is not None and i == self._first_graph_step and o.sig != self._graph_sig():
+            o.drop_graphs()                               # (a verbose run after a silent one: capture again)
         if o.graphs is None:
             self._capture(i)                              # captures AND performs iteration i
             return

@@ -297,14 +297,14 @@ def _msf_logits(model, x):
 
 def _score_buffer(model, shape, device):
     try:
-        bufs = _MSF_SCORE.setdefault(model, {})
+        held = _MSF_SCORE.setdefault(model, {})
     except TypeError:
-        bufs = {}
+        held = {}
     key = (*shape, str(device))
-    if key not in bufs:
-        bufs.clear()                         # one batch shape at a time (the last batch of a loader may be smaller)
-        bufs[key] = torch.empty(shape, dtype=torch.float32, device=device)
-    return bufs[key].zero_()
+    if key not in held:
+        held.clear()                         # one batch shape at a time (the last batch of a loader may be smaller)
+        held[key] = torch.empty(shape, dtype=torch.float32, device=device)
+    return held[key].zero_()
 
 
 @torch.no_grad()

@@ -384,8 +384,8 @@ def test_hip_graph_mode_on_images_whose_size_is_not_a_multiple_of_four(capfd):
 
 
 def test_one_captured_graph_pair_serves_every_stage_loss_and_batch(A):
-    """Round 5: the radius, the run length and the checkpoint table are device state (sea_apgd_linf_step_graph_dev /
-    sea_apgd_track_graph_dev) and the buffers a captured graph addresses live in a slot of the model: ONE capture serves the
+    """Round 5: the radius, the run length and the checkpoint table are device state (sea_apgd_linf_step_graph /
+    sea_apgd_track_graph) and the buffers a captured graph addresses live in a slot of the model: ONE capture serves the
     nine apgd_train calls of a SEA batch (three losses x three stages of different radius and length, reference
     attacker.py:691-728, tools/infer.py:338-370) and the next batch of the same shape -- with the bits of a capture per run."""
     from oracle.tiny_models import make_labels
@@ -438,6 +438,96 @@ def test_one_captured_graph_pair_serves_every_stage_loss_and_batch(A):
     assert not torch.equal(cached[0][0], cached[1][0])
     A.release_graph_cache(net)
     assert net not in A._GRAPH_SLOTS
+
+
+_STEP_CALLS = ("apgd_linf_step", "apgd_linf_step_graph", "apgd_track", "apgd_track_graph", "select_copy", "loss_fwd_bwd")
+
+
+@pytest.fixture(scope="module")
+def step_modes(A):
+    """One 14-iteration L-inf attack on PointwiseNet run three ways -- every iteration executed, capturing the graph pair,
+    replaying the cached pair from iteration 0 -- with the attack-side kernel calls of every step recorded."""
+    from oracle.tiny_models import make_labels
+    net = PointwiseNet(21, seed=13)
+    g = torch.Generator().manual_seed(29)
+    x = torch.rand(3, 3, 7, 9, generator=g)
+    y = make_labels(net, x, ignore_frac=0.05, flip_frac=0.1, seed=4).cuda()
+    net, x = net.cuda(), x.cuda()
+    w = torch.rand(21, generator=g).cuda()
+    n_iter, calls = 14, []
+    real = {k: getattr(A.N, k) for k in _STEP_CALLS}
+    real_capture = A.ApgdRun._capture
+
+    def recorder(name):
+        def f(*a, **k):
+            calls.append(name)
+            return real[name](*a, **k)
+        return f
+
+    def capture(self, i):
+        calls.append("capture begins")
+        real_capture(self, i)
+        calls.append("capture ends")
+
+    def attack(graph):
+        A.USE_HIP_GRAPH = graph
+        del calls[:]
+        run = A.ApgdRun(net, x, y, 8.0 / 255, n_iter, "mask-ce-bal", "ce-avg", False, 21, w, x.clone())
+        try:
+            run.start()
+            marks = [len(calls)]
+            for i in range(n_iter):
+                run.step(i)
+                marks.append(len(calls))
+            out = dict(start=calls[:marks[0]], steps=[calls[a:b] for a, b in zip(marks, marks[1:])],
+                       it_dev=int(run.own.it_dev), result=run.result(), first_graph_step=run._first_graph_step)
+        finally:
+            run.release_graphs()
+        return out
+
+    old = A.USE_HIP_GRAPH
+    for k in _STEP_CALLS:
+        setattr(A.N, k, recorder(k))
+    A.ApgdRun._capture = capture
+    try:
+        A.release_graph_cache(net)
+        modes = {"eager": attack(False), "capturing": attack(True), "replaying": attack(True)}
+    finally:
+        A.USE_HIP_GRAPH, A.ApgdRun._capture = old, real_capture
+        for k in _STEP_CALLS:
+            setattr(A.N, k, real[k])
+        A.release_graph_cache(net)
+    return modes
+
+
+def test_eager_and_captured_steps_make_the_same_attack_side_calls(step_modes):
+    """An iteration is one sequence of calls -- in-place K1, K2, device-word K7, K4 -- that is either executed or recorded:
+    the L-inf loop never calls the out-of-place K1, calls the host-scalar K7 exactly once (`init`, in start()), and what
+    `_capture` records is what an executed iteration calls.  A replayed iteration calls K2 only."""
+    one = ["apgd_linf_step_graph", "loss_fwd_bwd", "apgd_track_graph", "select_copy"]
+    for tag, m in step_modes.items():
+        every = m["start"] + [c for st in m["steps"] for c in st]
+        assert "apgd_linf_step" not in every, tag
+        assert every.count("apgd_track") == 1 and m["start"] == ["loss_fwd_bwd", "apgd_track"], tag
+    assert all(st == one for st in step_modes["eager"]["steps"])
+    cap = step_modes["capturing"]
+    assert cap["first_graph_step"] == 2 and step_modes["replaying"]["first_graph_step"] == 0
+    assert cap["steps"][0] == one and cap["steps"][1] == one and cap["steps"][-1] == one
+    assert cap["steps"][2] == ["capture begins"] + one + ["capture ends"]
+    assert all(st == ["loss_fwd_bwd"] for st in cap["steps"][3:-1])
+    rep = step_modes["replaying"]["steps"]
+    assert all(st == ["loss_fwd_bwd"] for st in rep[:-1]) and rep[-1] == one
+
+
+def test_the_loop_index_is_device_state_in_every_mode(step_modes):
+    """Nothing on the host writes the loop index after the run's reset: K1 reads it, K7 advances it, whether the iteration
+    is executed, captured or replayed (from iteration 0 with a cached pair).  After start() + n_iter steps it reads n_iter,
+    and the three runs return the same bits."""
+    for tag, m in step_modes.items():
+        assert m["it_dev"] == len(m["steps"]) == 14, tag
+    for tag in ("capturing", "replaying"):
+        for a, b in zip(step_modes["eager"]["result"], step_modes[tag]["result"]):
+            assert torch.equal(a, b), tag
 
 
 @pytest.mark.parametrize("amp", [False, True])

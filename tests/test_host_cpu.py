@@ -34,7 +34,7 @@ def test_library_exports_every_declared_symbol(native):
     assert declared <= exported, declared - exported
     assert declared == set(native.EXPORTS)
     lib = native.lib()  # binds every prototype; AttributeError on ABI drift
-    assert lib.sea_abi_version() == 2
+    assert lib.sea_abi_version() == 3
     assert b"gfx950" in lib.sea_build_info()
     assert lib.sea_loss_workspace_bytes(8, 512 * 512) == (8 * 2048 + 1) * 16  # header + one record per 128-pixel tile (the smallest tile any K2 variant uses)
 
@@ -45,7 +45,8 @@ def test_library_is_stateless(native):
     api_misc.cpp) and holds no atomics or mutable namespace-scope variables to dispatch on."""
     out = subprocess.run(["nm", "-D", "--defined-only", native.LIB_PATH], capture_output=True, text=True, check=True).stdout
     exported = set(re.findall(r" T (sea_\w+)", out))
-    gone = {"sea_gemm_split_pipeline", "sea_gemm_split_mfma_shape", "sea_attention_fwd", "sea_attention_bwd"}
+    gone = {"sea_gemm_split_pipeline", "sea_gemm_split_mfma_shape", "sea_attention_fwd", "sea_attention_bwd",
+            "sea_apgd_linf_step_graph_dev", "sea_apgd_track_graph_dev"}
     assert not (gone & exported) and not (gone & set(native.EXPORTS))
     csrc = os.path.join(PKG, "csrc")
     # a definition at namespace scope that is not const / constexpr: `static int g_x = ...;`, `std::atomic<int> g{...};`

@@ -71,12 +71,13 @@ def test_linf_kernels_vs_oracle(N, shape):
 
 @pytest.mark.parametrize("hw", [(9, 7), (8, 8)])     # 3*H*W odd: one float per lane; a multiple of four: float4
 def test_replayable_k1_k7_with_scalar_arguments_and_with_device_words_agree(N, hw):
-    """The replayable K1 / K7 of the HIP-graph mode (loop index and checkpoint table in device memory) come in two forms:
-    radius and run length as launch arguments (sea_apgd_linf_step_graph / sea_apgd_track_graph), or as device words too
-    (the _dev pair, which ApgdRun captures; its tables are sized for the longest run replayed).  The same seeded buffers go
+    """K1 / K7 come in two forms: the reference-shaped one with host scalars (sea_apgd_linf_step writes a third buffer and the
+    caller rotates; sea_apgd_track takes iter, n_iter and check_k as arguments) and the replayable one that the attack loop
+    runs (sea_apgd_linf_step_graph updates x_adv / x_old in place; sea_apgd_track_graph reads radius, run length, loop index
+    and checkpoint table from device memory, its tables sized for the longest run replayed).  The same seeded buffers go
     through both for five iterations of a 12-step schedule -- a = 1 at iteration 0, the window-2 checkpoint at iteration 1
-    with one image that halves its step and restarts and one that does not -- and every output buffer is bit-identical
-    after every iteration."""
+    with one image that halves its step and restarts and one that does not -- and every buffer (x_adv / x_old by role, not
+    by address) and every state field is bit-identical after every iteration."""
     from semseg import attacker as A
     (H, W), B, n_iter, cap, eps, steps = hw, 3, 12, 16, 8.0 / 255, 5
     HW = H * W
@@ -96,22 +97,31 @@ def test_replayable_k1_k7_with_scalar_arguments_and_with_device_words_agree(N, h
         rows = cap if device_words else n_iter
         st = A.ApgdState(B, rows, eps, "cuda")
         b = dict(x_adv=x0.cuda(), x_old=x0.cuda(), grad=grads[0].cuda(), x_best=x0.cuda(), x_best_adv=x0.cuda(),
-                 grad_best=grads[0].cuda(), pred=preds[0].cuda(), pred_best=preds[0].cuda(),
-                 it_dev=torch.zeros(1, dtype=torch.int32, device="cuda"))
+                 grad_best=grads[0].cuda(), pred=preds[0].cuda(), pred_best=preds[0].cuda())
+        if device_words:
+            b["it_dev"] = torch.zeros(1, dtype=torch.int32, device="cuda")
         stats = lambda i: dict(loss_sum=tracks[i].cuda(), track_sum=tracks[i].cuda(), n_correct=corr[i].cuda())  # noqa: E731
         N.apgd_track(stats(0), n_ign, HW, 0, n_iter, 0, True, True, st)       # step 0 of a run
         tab = torch.zeros(rows, dtype=torch.int32)
         for k, v in cps.items():
             tab[k] = v
         tab, xd = tab.cuda(), x.cuda()
-        eps_arg = torch.full((1,), eps, dtype=torch.float32, device="cuda") if device_words else eps
-        n_arg = torch.full((1,), n_iter, dtype=torch.int32, device="cuda") if device_words else n_iter
+        eps_dev = torch.full((1,), eps, dtype=torch.float32, device="cuda")
+        n_dev = torch.full((1,), n_iter, dtype=torch.int32, device="cuda")
+        x_next = torch.empty_like(xd)                                       # (a): the third iterate buffer
         snaps = []
         for i in range(steps):
-            N.apgd_linf_step_graph(xd, b["x_adv"], b["x_old"], b["grad"], st.step, eps_arg, b["it_dev"])
+            if device_words:
+                N.apgd_linf_step_graph(xd, b["x_adv"], b["x_old"], b["grad"], st.step, eps_dev, b["it_dev"])
+            else:
+                N.apgd_linf_step(xd, b["x_adv"], b["x_old"], b["grad"], st.step, eps, 0.75 if i > 0 else 1.0, out=x_next)
+                b["x_old"], b["x_adv"], x_next = b["x_adv"], x_next, b["x_old"]
             b["grad"].copy_(grads[i + 1])                                   # (what the model's backward would leave)
             b["pred"].copy_(preds[i + 1])
-            N.apgd_track_graph(stats(i + 1), n_ign, HW, b["it_dev"], tab, n_arg, True, st)
+            if device_words:
+                N.apgd_track_graph(stats(i + 1), n_ign, HW, b["it_dev"], tab, n_dev, True, st)
+            else:
+                N.apgd_track(stats(i + 1), n_ign, HW, i, n_iter, cps.get(i, 0), True, False, st)
             N.select_copy(st.flags, b["x_adv"], b["grad"], b["x_best"], b["grad_best"], b["x_best_adv"], b["pred"], b["pred_best"])
             snap = {k: v.clone() for k, v in b.items()}
             snap.update({k: getattr(st, k).clone() for k in ("acc_cnt", "acc", "loss_best", "loss_best_last", "reduced_last",
@@ -122,11 +132,12 @@ def test_replayable_k1_k7_with_scalar_arguments_and_with_device_words_agree(N, h
 
     scalar, words = drive(False), drive(True)
     for i, (s, d) in enumerate(zip(scalar, words)):
+        assert set(d) == set(s) | {"it_dev"}
         for k in s:
             assert torch.equal(s[k], d[k]), (i, k)
-    last = scalar[-1]
+    last = words[-1]
     assert int(last["it_dev"]) == steps and not torch.equal(last["x_adv"], x0.cuda())
-    assert last["step"][1] < last["step"][0] == scalar[0]["step"][0]          # image 1 was halved, image 0 never
+    assert last["step"][1] < last["step"][0] == words[0]["step"][0]           # image 1 was halved, image 0 never
 
 
 # ------------------------------------------------------------------------------------------------ K2

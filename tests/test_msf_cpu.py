@@ -80,7 +80,7 @@ def test_msf_symbols_exported_with_c_signatures(native):
     out = subprocess.run(["nm", "-D", "--defined-only", native.LIB_PATH], capture_output=True, text=True, check=True).stdout
     assert re.search(r" T sea_msf_resize_input$", out, flags=re.M) and re.search(r" T sea_msf_accumulate$", out, flags=re.M)
     lib = native.lib()
-    assert lib.sea_abi_version() == 2
+    assert lib.sea_abi_version() == 3
     # argument checks fire on the host before any launch: invalid arguments return 1 (no device needed)
     assert lib.sea_msf_resize_input(None, None, None, 1, 4, 4, 8, 8, None) == 1
     assert lib.sea_msf_accumulate(None, None, 1, 5, 4, 4, 8, 8, 8, 8, 0, None) == 1
