@@ -198,6 +198,50 @@ def loss_fwd_bwd(logits, y, weights, mode, track_mode=None, with_grad=True, igno
     return out
 
 
+def loss_eval_f64(logits, y, weights=None, mode: int = MODE_MASK_CE, track_mode: Optional[int] = None):
+    """float64 restatement of what K2 WITHOUT gradient returns (include/sea_hip.h, dlogits = NULL), for the kernel tests.
+
+    The logits are taken as given: a bf16 / fp16 tensor is its own, already rounded, input and is widened exactly.  Labels
+    may have any integer type; a label outside [0, C) -- -1, 255 of a uint8 map, anything >= C -- is ignored, as the header
+    says.  Class weights are the fp32 values, widened.
+
+    Returns dict(pred, n_correct, loss_px, track_px, loss_sum, track_sum):
+      pred        torch.max over the classes on the tensor's own type: the first NaN, else the first maximum
+      n_correct   (B) int64, valid pixels with pred == label
+      loss_px     (B,H,W) float64 per-pixel attack loss; track_px the same for the tracking mode
+      loss_sum / track_sum  (B) float64 sums over ALL pixels of the image (the caller divides by H*W)
+    """
+    B, C = logits.shape[:2]
+    pred = logits.max(1)[1]
+    z = logits.double()
+    yl = y.long()
+    valid = (yl >= 0) & (yl < C)
+    ys = torch.where(valid, yl, torch.zeros_like(yl))
+    correct = valid & (pred == ys)
+    lse = torch.logsumexp(z, dim=1)
+    zy = z.gather(1, ys.unsqueeze(1)).squeeze(1)
+    ce = lse - zy
+    zero = torch.zeros_like(ce)
+
+    def px(m):
+        if m == MODE_CE:
+            return torch.where(valid, ce, zero)
+        if m == MODE_MASK_CE:
+            return torch.where(correct, ce, zero)
+        if m == MODE_MASK_CE_BAL:
+            return torch.where(correct, weights.double()[ys] * ce, zero)
+        if m == MODE_JS:
+            logp = zy - lse
+            py = torch.exp(logp)
+            return torch.where(valid, LN2 + 0.5 * (py * logp - (1.0 + py) * torch.log1p(py)), zero)
+        raise ValueError(m)
+
+    lp = px(mode)
+    tp = lp if track_mode is None or track_mode == mode else px(track_mode)
+    return dict(pred=pred, n_correct=correct.reshape(B, -1).sum(-1), loss_px=lp, track_px=tp,
+                loss_sum=lp.reshape(B, -1).sum(-1), track_sum=tp.reshape(B, -1).sum(-1))
+
+
 def loss_fwd_bwd_upsampled(low, y, weights, mode, track_mode=None, with_grad=True, ignored_correct=True):
     """K2u: bilinear upsample of the low-res logits to the label resolution
     (semseg/models/uperforseg.py:416-418, segmenter.py:228) followed by everything K2 computes; the

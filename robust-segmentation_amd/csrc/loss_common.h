@@ -89,6 +89,33 @@ __device__ __forceinline__ float grad_coef(int mode, bool valid, bool correct, f
   return correct ? wy : 0.f;
 }
 
+// torch.max over the classes of ONE pixel of an NCHW tensor, read straight from memory: the first NaN wins, else the first
+// maximum.  The cold path behind a NaN soft-max sum.  Kernels that keep exp(z - m) in place of z need it: a NaN among the
+// e's marks a NaN logit OR a +inf one (inf - inf), so the e's alone cannot tell a +inf that precedes a NaN from the NaN
+// that torch returns.
+template <typename T>
+__device__ __forceinline__ int torch_argmax_from_memory(const T* __restrict__ px_base, int C, int64_t HW) {
+  using R = typename Elem<T>::raw;
+  const R* p = reinterpret_cast<const R*>(px_base);
+  float m = Elem<T>::to_f(p[0]);
+  int arg = 0;
+#pragma unroll 1
+  for (int c = 1; c < C; ++c) {
+    const float z = Elem<T>::to_f(p[(int64_t)c * HW]);
+    if (!(z <= m) && !(m != m)) {
+      m = z;
+      arg = c;
+    }
+  }
+  return arg;
+}
+// The same out of line, for kernels at a register cliff (the register-resident and the streaming kernel): inlined, the
+// loop's live values spill in their hot paths; loss_split.hip allocates better with the loop inlined.
+template <typename T>
+__device__ __noinline__ int slow_torch_argmax(const T* __restrict__ px_base, int C, int64_t HW) {
+  return torch_argmax_from_memory<T>(px_base, C, HW);
+}
+
 // block reduction of the three per-thread sums and record write (fixed order, deterministic).
 // Workspace layout: record 0 is a header {tiles per image, images, 0, 0} written by block (0,0); the
 // per-block records follow, image-major.  The header lets the consumer (loss_finalize or the APGD

@@ -105,6 +105,9 @@ __global__ __launch_bounds__(256, (TUNE & 4) ? 4 : 1) void loss_nchw_reg(const T
     // be complete first; without it the compiler runs exp early into fresh registers and keeps
     // BOTH z and exp(z-m) alive (2x the register file, half the occupancy).
     asm volatile("" : "+v"(m) : "v"(arg), "v"(zy));
+    // From here on the maximum is kept finite (any finite maximum is unchanged).  Under a maximum of +-inf exp(z - m) would
+    // be NaN at the +-inf logits themselves (inf - inf); with the clamp it is +inf or 0 there and NaN at NaN logits only.
+    m = fminf(fmaxf(m, -3.402823466e38f), 3.402823466e38f);
     float s = 0.f;
 #pragma unroll
     for (int c = 0; c < CPAD; ++c) {
@@ -113,9 +116,9 @@ __global__ __launch_bounds__(256, (TUNE & 4) ? 4 : 1) void loss_nchw_reg(const T
       s += e;
     }
     // torch.max semantics for non-finite logits (reference attacker.py:145, 370, 485): the first NaN wins, else the
-    // first maximum.  The fmaxf chain above ignores NaNs, but then exp(z - m) is NaN exactly at the NaN logits (and
-    // at the +inf logits when the maximum is +inf, and everywhere when all logits are -inf), so the sum flags the
-    // case and the first NaN among the e's is torch's index in all of them.  Never taken for finite logits.
+    // first maximum.  The fmaxf chain above ignores NaNs and the scan gives the first maximum, +-inf included; exp(z - m)
+    // with the clamped m is NaN exactly at the NaN logits, so the sum flags them and the first NaN among the e's is
+    // torch's index.  (Without the clamp a +inf ahead of a NaN was a NaN too and won.)  Never taken for finite logits.
     if (__builtin_expect(s != s, 0)) {
 #pragma unroll
       for (int c = CPAD - 1; c >= 0; --c) arg = (z[c][v] != z[c][v]) ? c : arg;
@@ -217,7 +220,8 @@ __global__ __launch_bounds__(256) void loss_nchw_stream(const T* __restrict__ lo
         m = zc;
         arg = c;
       } else {
-        s += __expf(zc - m);
+        // a -inf logit adds nothing; under a running maximum of -inf (masked leading classes) exp(-inf - -inf) would be NaN
+        s += (zc == -INFINITY) ? 0.f : __expf(zc - m);
       }
     }
     const bool valid = lab >= 0;

@@ -109,32 +109,21 @@ __global__ __launch_bounds__(256, WAVES) void loss_nchw_split(const T* __restric
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    int arg = cbase + argj;
-    // NaN / +-inf logits: the first NaN among the e's is torch.max's index.  (Inactive tail lanes hold -inf everywhere,
-    // exp(-inf - -inf) = NaN: they must not drag the wave into the cold path.)
-    if (__builtin_expect(active && s != s, 0)) {
-      int an = 0x7fffffff;
-#pragma unroll
-      for (int j = CH - 1; j >= 0; --j) {
-        const float e = (PPW == 1) ? __uint_as_float(raw[j]) : __expf(Word<T>::get(raw[j], h) - m);
-        an = (e != e) ? cbase + j : an;
-      }
-      arg = an != 0x7fffffff ? an : arg;
-    }
+    const int arg = cbase + argj;
     // ---- merge the two halves (lane l <-> lane l + 32) ------------------------------------------------------------
     const float m_o = __shfl_xor(m, 32, 64);
     const float s_o = __shfl_xor(s, 32, 64);
     const int arg_o = __shfl_xor(arg, 32, 64);
     const float zy_o = __shfl_xor(zy, 32, 64);
-    const bool s_bad = (s != s), so_bad = (s_o != s_o);
-    // torch.max over both halves: a half holding a NaN wins (the lower class index if both do); otherwise the larger
-    // maximum, the lower index on ties
-    bool other;
-    if (s_bad || so_bad)
-      other = so_bad && (!s_bad || arg_o < arg);
-    else
-      other = (m_o > m) || (m_o == m && arg_o < arg);
-    const int arg_t = other ? arg_o : arg;
+    // torch.max over both halves: the larger maximum, the lower index on ties
+    const bool other = (m_o > m) || (m_o == m && arg_o < arg);
+    int arg_t = other ? arg_o : arg;
+    // NaN / +-inf logits flag themselves through the sum of either half (exp(z - m) is NaN at a NaN, at +inf - +inf and at
+    // -inf - -inf).  The e's cannot tell a +inf from a NaN, nor can one half know of a NaN in the other, so torch.max's
+    // index (the first NaN, else the first maximum) is taken from the logits in memory; both halves of a pixel get here
+    // together.  (Inactive tail lanes hold -inf everywhere and flag too: they must not read.)
+    if (__builtin_expect(active && (s != s || s_o != s_o), 0))
+      arg_t = torch_argmax_from_memory<T>(logits + (int64_t)b * C * HW + px0 + h, C, HW);
     const float M = fmaxf(m, m_o);
     const float me = (M == -INFINITY) ? -3.0e38f : M;                    // all logits -inf: keep exp(-inf - -inf) out
     const float r_own = __expf(((m == -INFINITY) ? -3.0e38f : m) - me);   // exp(m_half - M) <= 1

@@ -11,24 +11,6 @@
 
 namespace sea {
 
-// torch.max over the classes of ONE pixel read straight from memory (first NaN wins, else first maximum): the
-// cold path behind a NaN soft-max sum.
-template <typename T>
-__device__ __noinline__ int slow_torch_argmax(const T* __restrict__ px_base, int C, int64_t HW) {
-  using R = typename Elem<T>::raw;
-  const R* p = reinterpret_cast<const R*>(px_base);
-  float m = Elem<T>::to_f(p[0]);
-  int arg = 0;
-  for (int c = 1; c < C; ++c) {
-    const float z = Elem<T>::to_f(p[(int64_t)c * HW]);
-    if (!(z <= m) && !(m != m)) {
-      m = z;
-      arg = c;
-    }
-  }
-  return arg;
-}
-
 // ---- NCHW, no gradient: streaming class loop ------------------------------------------------------------------
 // Without a gradient nothing has to survive the class loop, so the class vector is NOT kept in registers: the
 // planes stream through a double-buffered chunk of CH 16-byte loads per lane while the previous chunk is folded
