@@ -127,12 +127,37 @@ int sea_loss_fwd_bwd(const void* logits, int dtype, int layout, const void* y, i
                      float grad_scale, void* dlogits, void* pred, int pred_bytes, float* loss_px,
                      void* workspace, size_t workspace_bytes, float* loss_sum, float* track_sum,
                      int32_t* n_correct, void* stream);
-/* Benchmark hook: identical, but pins the pixels-per-lane (1/2/4, 0 = heuristic) of the register kernel. */
+/* The same with a variant word that pins the kernel (tests, A/B runs); 0 = sea_loss_fwd_bwd.  Fields:
+ *   SEA_K2_VEC_MASK      bits 0-3: pixels per lane of the register kernel, 1 | 2 | 4 (0 = the widest that H*W and the pointers'
+ *                        alignment allow); a non-zero value also keeps the streaming and the split kernel out.
+ *   SEA_K2_TUNE_SHIFT    bits 4-7: TUNE of the register kernel (1 = non-temporal gradient stores, 2 = non-temporal logit loads,
+ *                        4 = 4 waves/SIMD).  Three fp32 cells have one: 7 at C = 21 with gradient, 6 at C = 21 without, 2 at
+ *                        C = 151 with gradient, each the default of a word whose low 12 bits are 0; 15 = none.  Ignored elsewhere.
+ *   SEA_K2_STREAM_SHIFT  bits 8-11: 1..4 = the streaming no-gradient kernel at any C, with (classes per chunk, waves/SIMD) =
+ *                        (4, 5), (8, 3), (6, 4), (2, 8).  SEA_K2_NO_SPLIT (15 in this field): not the split kernel (gradient
+ *                        at C = 150 / 151), the register kernel instead.
+ *   SEA_K2_REG_ONLY      bit 12: neither the streaming nor the split kernel.
+ * A word whose field names nothing (other bits, a TUNE without instantiation, a streaming variant where the split kernel would
+ * run) is an invalid argument. */
+#define SEA_K2_VARIANT_DEFAULT 0u
+#define SEA_K2_VEC_MASK 0xfu
+#define SEA_K2_TUNE_SHIFT 4
+#define SEA_K2_STREAM_SHIFT 8
+#define SEA_K2_NO_SPLIT (15u << SEA_K2_STREAM_SHIFT)
+#define SEA_K2_REG_ONLY 0x1000u
 int sea_loss_fwd_bwd_tuned(const void* logits, int dtype, int layout, const void* y, int y_bytes,
                            const float* w, int mode, int track_mode, int B, int C, int64_t HW,
                            float grad_scale, void* dlogits, void* pred, int pred_bytes, float* loss_px,
                            void* workspace, size_t workspace_bytes, float* loss_sum, float* track_sum,
-                           int32_t* n_correct, void* stream, int force_vec);
+                           int32_t* n_correct, void* stream, int variant);
+/* host only, touches no device: the kernel a call with these arguments runs (csrc/loss_plan.h).  Only the alignment of the two
+ * addresses matters; dlogits_addr is read when want_grad != 0.  Returns what the call would return for them (0, or 1 for a
+ * shape or word without kernel) and fills out = {kernel, cpad, exact, vec, tune, ch, waves, tiles}: kernel 0 = register
+ * (cpad class registers, vec pixels per lane, exact: C == cpad), 1 = two-pass (C > 192), 2 = streaming no-gradient (ch classes
+ * per chunk), 3 = split, 4 = channels_last; waves = waves/SIMD asked of the compiler where the kernel has the knob; tiles =
+ * blocks, and workspace records, per image. */
+int sea_loss_plan(int dtype, int layout, int C, int64_t HW, int want_grad, size_t logits_addr, size_t dlogits_addr,
+                  unsigned variant, int32_t out[8]);
 
 /* K2u  K2 fused with the model's final bilinear upsample.
  * replaces  F.interpolate(logits, size=(H,W), mode="bilinear", align_corners=False)

@@ -1,7 +1,8 @@
 // Shared pieces of the K2 translation units (loss_kernels.hip: register-resident and layout variants + the C ABI;
-// loss_stream.hip: streaming no-gradient kernel and packed 16-bit gradient kernel).
+// loss_stream.hip: streaming no-gradient kernel; loss_split.hip: ADE-sized gradient kernel; loss_plan.h: which one runs).
 #pragma once
 #include "sea_common.h"
+#include "loss_plan.h"
 
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
@@ -165,7 +166,6 @@ struct LossArgs {
   float* loss_px;
   BlockPartial* partials;
   hipStream_t s;
-  int force_vec;
 };
 
 static inline int tiles_for(int64_t HW, int vec) { return (int)((HW + 256 * vec - 1) / (256 * (int64_t)vec)); }
@@ -251,9 +251,9 @@ __device__ __forceinline__ void fence_word(uint32_t& w) { asm volatile("" : "+v"
 
 // loss_stream.hip
 template <typename T>
-void launch_fwd(const LossArgs& a, int variant);
+int launch_fwd(const LossArgs& a, const LossPlan& p);
 // loss_split.hip: ADE-sized class vectors (C = 150 / 151) split over the two halves of a wave
 template <typename T>
-bool dispatch_split(const LossArgs& a, int* tiles_used);
+int launch_split(const LossArgs& a, const LossPlan& p);
 
 }  // namespace sea

@@ -363,223 +363,60 @@ __global__ __launch_bounds__(256) void loss_finalize(const BlockPartial* __restr
   }
 }
 
-// ---- dispatch --------------------------------------------------------------------------------------
+// ---- launch ----------------------------------------------------------------------------------------
+// The launchers decide nothing: kernel, template parameters and grid come from the plan (loss_plan.h).
+#define SEA_K2_ARGS(T) \
+  (const T*)a.logits, a.y, a.y_bytes, a.w, a.mode, a.track_mode, a.C, a.HW, a.gscale, (T*)a.dlogits, a.pred, a.pred_bytes
+
 template <typename T, int CPAD, int VEC>
-static void launch_reg(const LossArgs& a) {
-  dim3 grid(tiles_for(a.HW, VEC), a.B), block(256);
-#define SEA_GO(G, E)                                                                                    \
-  hipLaunchKernelGGL((loss_nchw_reg<T, CPAD, VEC, G, E>), grid, block, 0, a.s, (const T*)a.logits, a.y, \
-                     a.y_bytes, a.w, a.mode, a.track_mode, a.C, a.HW, a.gscale, (T*)a.dlogits, a.pred,  \
-                     a.pred_bytes, a.loss_px, a.partials)
-  const bool exact = (a.C == CPAD);
-  if (a.dlogits) {
-    if (exact)
-      SEA_GO(true, true);
-    else
-      SEA_GO(true, false);
-  } else {
-    if (exact)
-      SEA_GO(false, true);
-    else
-      SEA_GO(false, false);
-  }
-#undef SEA_GO
-}
-
-template <typename T>
-static void launch_stream(const LossArgs& a) {
-  dim3 grid(tiles_for(a.HW, 1), a.B), block(256);
-  if (a.dlogits)
-    hipLaunchKernelGGL((loss_nchw_stream<T, true>), grid, block, 0, a.s, (const T*)a.logits, a.y, a.y_bytes, a.w,
-                       a.mode, a.track_mode, a.C, a.HW, a.gscale, (T*)a.dlogits, a.pred, a.pred_bytes, a.loss_px, a.partials);
-  else
-    hipLaunchKernelGGL((loss_nchw_stream<T, false>), grid, block, 0, a.s, (const T*)a.logits, a.y, a.y_bytes, a.w,
-                       a.mode, a.track_mode, a.C, a.HW, a.gscale, (T*)nullptr, a.pred, a.pred_bytes, a.loss_px, a.partials);
-}
-
-template <typename T>
-static int launch_nhwc(const LossArgs& a) {
-  const int CS = a.C | 1;  // odd row stride (in dwords): lanes hit distinct banks
-  const size_t lds = (size_t)256 * CS * sizeof(float);
-  if (lds > 160 * 1024 - 64) return SEA_ERR_ARG;
-  dim3 grid(tiles_for(a.HW, 1), a.B), block(256);
-  if (a.dlogits) {
-    auto k = loss_nhwc_lds<T, true>;
-    if (lds > 48 * 1024)
-      (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k, grid, block, lds, a.s, (const T*)a.logits, a.y, a.y_bytes, a.w, a.mode, a.track_mode, a.C,
-                       CS, a.HW, a.gscale, (T*)a.dlogits, a.pred, a.pred_bytes, a.loss_px, a.partials);
-  } else {
-    auto k = loss_nhwc_lds<T, false>;
-    if (lds > 48 * 1024)
-      (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k, grid, block, lds, a.s, (const T*)a.logits, a.y, a.y_bytes, a.w, a.mode, a.track_mode, a.C,
-                       CS, a.HW, a.gscale, (T*)nullptr, a.pred, a.pred_bytes, a.loss_px, a.partials);
-  }
+static int launch_reg_as(const LossArgs& a, const LossPlan& p) {
+  const bool g = a.dlogits != nullptr;
+  auto k = g ? (p.exact ? loss_nchw_reg<T, CPAD, VEC, true, true> : loss_nchw_reg<T, CPAD, VEC, true, false>)
+             : (p.exact ? loss_nchw_reg<T, CPAD, VEC, false, true> : loss_nchw_reg<T, CPAD, VEC, false, false>);
+  // the three fp32 TUNE instantiations that ship (loss_plan.h), each of them EXACT; 0 elsewhere = the kernels above
+  constexpr bool voc = sizeof(T) == 4 && CPAD == 21 && VEC == 4, ade = sizeof(T) == 4 && CPAD == 151;
+  if (p.tune) k = g ? loss_nchw_reg<T, CPAD, VEC, true, true, voc ? 7 : ade ? 2 : 0> : loss_nchw_reg<T, CPAD, VEC, false, true, voc ? 6 : 0>;
+  hipLaunchKernelGGL(k, dim3(p.tiles, a.B), dim3(256), 0, a.s, SEA_K2_ARGS(T), a.loss_px, a.partials);
   return 0;
 }
 
-// choose the register-resident variant: exact-C instantiations for the datasets of the reference
-// (VOC 21, ADE 151/150, Cityscapes 19), otherwise the smallest CPAD >= C.
 template <typename T>
-static int dispatch_nchw(const LossArgs& a, bool vec4_ok, bool vec2_ok, int* vec_used) {
-  const int C = a.C;
-#define SEA_REG(CP, V)       \
-  do {                       \
-    launch_reg<T, CP, V>(a); \
-    *vec_used = V;           \
-    return 0;                \
-  } while (0)
-  // force_vec: low 4 bits 0 = heuristic, 1/2/4 = pixels per lane; bits 4.. = TUNE variant (fp32 C=21/151 only)
-  const int fv = a.force_vec & 15;
-  int tune = (a.force_vec >> 4) & 15;
-  // measured defaults (kernel_bench, MI355X): C=21 fp32 runs best with non-temporal loads+stores at 4
-  // waves/SIMD (74 % of 8 TB/s vs 65 %), C=151 with non-temporal loads (69 % vs 67.6 %)
-  if ((a.force_vec & 0xfff) == 0 && sizeof(T) == 4 && a.dlogits) tune = (C == 21 && vec4_ok) ? 7 : (C == 151 ? 2 : 0);
-  if ((a.force_vec & 0xfff) == 0 && sizeof(T) == 4 && !a.dlogits && C == 21 && vec4_ok) tune = 6;
-  if (tune == 15) tune = 0;  // explicit "no tuning" for A/B runs
-  if (tune == 6 && !a.dlogits && sizeof(T) == 4 && C == 21 && vec4_ok) {  // no-gradient: nt loads, 4 waves/SIMD
-    dim3 grid(tiles_for(a.HW, 4), a.B), block(256);
-    hipLaunchKernelGGL((loss_nchw_reg<T, 21, 4, false, true, 6>), grid, block, 0, a.s, (const T*)a.logits, a.y,
-                       a.y_bytes, a.w, a.mode, a.track_mode, a.C, a.HW, a.gscale, (T*)nullptr, a.pred, a.pred_bytes,
-                       a.loss_px, a.partials);
-    *vec_used = 4;
-    return 0;
-  }
-  if (tune && a.dlogits && sizeof(T) == 4) {
-    dim3 block(256);
-#define SEA_TUNED(CP, V, TU)                                                                                         \
-  do {                                                                                                               \
-    dim3 grid(tiles_for(a.HW, V), a.B);                                                                              \
-    hipLaunchKernelGGL((loss_nchw_reg<T, CP, V, true, true, TU>), grid, block, 0, a.s, (const T*)a.logits, a.y,      \
-                       a.y_bytes, a.w, a.mode, a.track_mode, a.C, a.HW, a.gscale, (T*)a.dlogits, a.pred,             \
-                       a.pred_bytes, a.loss_px, a.partials);                                                         \
-    *vec_used = V;                                                                                                   \
-    return 0;                                                                                                        \
-  } while (0)
-    if (C == 21 && vec4_ok) {
-      if (tune == 1) SEA_TUNED(21, 4, 1);
-      if (tune == 2) SEA_TUNED(21, 4, 2);
-      if (tune == 3) SEA_TUNED(21, 4, 3);
-      if (tune == 4) SEA_TUNED(21, 4, 4);
-      if (tune == 5) SEA_TUNED(21, 4, 5);
-      if (tune == 7) SEA_TUNED(21, 4, 7);
-    }
-    if (C == 151) {
-      if (tune == 1) SEA_TUNED(151, 1, 1);
-      if (tune == 2) SEA_TUNED(151, 1, 2);
-      if (tune == 3) SEA_TUNED(151, 1, 3);
-    }
-#undef SEA_TUNED
-  }
-  if (vec4_ok && (fv == 0 || fv == 4)) {
-    if (C <= 8) SEA_REG(8, 4);
-    if (C <= 16) SEA_REG(16, 4);
-    if (C == 19) SEA_REG(19, 4);
-    if (C == 21) SEA_REG(21, 4);
-    if (C <= 24) SEA_REG(24, 4);
-    if (C <= 32) SEA_REG(32, 4);
-  }
-  if (vec2_ok && (fv == 0 || fv == 2 || fv == 4)) {
-    if (C <= 8) SEA_REG(8, 2);
-    if (C <= 16) SEA_REG(16, 2);
-    if (C == 19) SEA_REG(19, 2);
-    if (C == 21) SEA_REG(21, 2);
-    if (C <= 24) SEA_REG(24, 2);
-    if (C <= 32) SEA_REG(32, 2);
-    if (C <= 48) SEA_REG(48, 2);
-    if (C <= 64) SEA_REG(64, 2);
-  }
-  if (C <= 8) SEA_REG(8, 1);
-  if (C <= 16) SEA_REG(16, 1);
-  if (C == 19) SEA_REG(19, 1);
-  if (C == 21) SEA_REG(21, 1);
-  if (C <= 24) SEA_REG(24, 1);
-  if (C <= 32) SEA_REG(32, 1);
-  if (C <= 48) SEA_REG(48, 1);
-  if (C <= 64) SEA_REG(64, 1);
-  if (C <= 96) SEA_REG(96, 1);
-  if (C <= 128) SEA_REG(128, 1);
-  if (C == 150) SEA_REG(150, 1);
-  if (C == 151) SEA_REG(151, 1);
-  if (C <= 160) SEA_REG(160, 1);
-  if (C <= 192) SEA_REG(192, 1);
+static int launch_reg(const LossArgs& a, const LossPlan& p) {
+  switch (p.cpad * 8 + p.vec) {
+#define SEA_REG(CP, V) \
+  case CP * 8 + V: return launch_reg_as<T, CP, V>(a, p);
+    SEA_K2_REG_INSTANCES(SEA_REG)
 #undef SEA_REG
-  launch_stream<T>(a);
-  *vec_used = 1;
+  }
+  return SEA_ERR_ARG;
+}
+
+template <typename T>
+static int launch_stream(const LossArgs& a, const LossPlan& p) {
+  auto k = a.dlogits ? loss_nchw_stream<T, true> : loss_nchw_stream<T, false>;
+  hipLaunchKernelGGL(k, dim3(p.tiles, a.B), dim3(256), 0, a.s, SEA_K2_ARGS(T), a.loss_px, a.partials);
   return 0;
 }
 
 template <typename T>
-static int dispatch_dtype(const LossArgs& a, int layout, int* tiles_used) {
-  const int y_bytes = a.y_bytes;
-  if (y_bytes != 8 && y_bytes != 4 && y_bytes != 2 && y_bytes != 1) return SEA_ERR_ARG;
-  if (layout == SEA_LAYOUT_NHWC) {
-    *tiles_used = tiles_for(a.HW, 1);
-    return launch_nhwc<T>(a);
-  }
-  if (layout != SEA_LAYOUT_NCHW) return SEA_ERR_ARG;
-  // vector width: every plane start (b*C+c)*HW + px0 must be VEC-element aligned
-  auto al = [&](int vec) {
-    const uintptr_t bytes = sizeof(T) * vec;
-    return (a.HW % vec) == 0 && (((uintptr_t)a.logits) % bytes) == 0 &&
-           (!a.dlogits || (((uintptr_t)a.dlogits) % bytes) == 0);
-  };
-  int vec = 1;
-  // force_vec bit 12: legacy register kernels only (A/B runs); bits 8..11: variant of the streaming kernel
-  const bool legacy = (a.force_vec & 0x1000) != 0;
-  constexpr int V16 = 16 / (int)sizeof(T);
-  // no gradient: beyond 32 classes the class vector no longer fits the registers at a useful occupancy -> streaming
-  // kernel (loss_stream.hip).  Measured cold (tools/k2_lab.py): C=151 fp32 200 us vs 225 us register kernel, bf16
-  // 130 us vs 165 us; at C=21 the register kernel (all 21 plane loads of a lane in flight at once) is as fast (fp32)
-  // or faster (16-bit: 28.5 vs 32.7 us) than the chunk pipeline, which pays one memory round trip per chunk.
-  const bool want_stream = a.C > 32 || ((a.force_vec >> 8) & 15) != 0;
-  if (!legacy && !a.dlogits && al(V16) && (a.force_vec & 15) == 0 && want_stream) {
-    launch_fwd<T>(a, (a.force_vec >> 8) & 15);
-    *tiles_used = tiles_for(a.HW, V16);
-    return 0;
-  }
-  // ADE-sized class vectors with gradient: split over the wave halves (loss_split.hip); variant 15 = skip (A/B runs)
-  if (!legacy && a.dlogits && (a.force_vec & 15) == 0 && ((a.force_vec >> 8) & 15) != 15 &&
-      dispatch_split<T>(a, tiles_used))
-    return 0;
-  const int rc = dispatch_nchw<T>(a, al(4), al(2), &vec);
-  *tiles_used = tiles_for(a.HW, vec);
-  return rc;
+static int launch_nhwc(const LossArgs& a, const LossPlan& p) {
+  auto k = a.dlogits ? loss_nhwc_lds<T, true> : loss_nhwc_lds<T, false>;
+  if (p.lds > 48 * 1024)
+    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+  hipLaunchKernelGGL(k, dim3(p.tiles, a.B), dim3(256), p.lds, a.s, (const T*)a.logits, a.y, a.y_bytes, a.w, a.mode,
+                     a.track_mode, a.C, a.C | 1, a.HW, a.gscale, (T*)a.dlogits, a.pred, a.pred_bytes, a.loss_px, a.partials);
+  return 0;
+}
+#undef SEA_K2_ARGS
+
+template <typename T>
+static int launch(const LossArgs& a, const LossPlan& p) {
+  constexpr int (*by_kernel[])(const LossArgs&, const LossPlan&) = {  // in K2Kernel's order
+      launch_reg<T>, launch_stream<T>, launch_fwd<T>, launch_split<T>, launch_nhwc<T>};
+  return by_kernel[p.kernel](a, p);
 }
 
-static int loss_fwd_bwd_impl(const void* logits, int dtype, int layout, const void* y, int y_bytes, const float* w,
-                             int mode, int track_mode, int B, int C, int64_t HW, float grad_scale, void* dlogits,
-                             void* pred, int pred_bytes, float* loss_px, void* workspace, size_t workspace_bytes,
-                             float* loss_sum, float* track_sum, int32_t* n_correct, void* stream, int force_vec) {
-  SEA_CHECK_ARG(logits && y && workspace);
-  // loss_sum == track_sum == n_correct == NULL: leave the per-block records in the workspace for
-  // sea_apgd_track (one launch less in the APGD loop)
-  const bool deferred = !loss_sum && !track_sum && !n_correct;
-  SEA_CHECK_ARG(deferred || (loss_sum && track_sum && n_correct));
-  SEA_CHECK_ARG(B > 0 && B <= 65535 && C > 0 && HW > 0);
-  SEA_CHECK_ARG(mode >= 0 && mode <= 3 && track_mode >= 0 && track_mode <= 3);
-  SEA_CHECK_ARG(!((mode == SEA_MODE_MASK_CE_BAL || track_mode == SEA_MODE_MASK_CE_BAL) && w == nullptr));
-  SEA_CHECK_ARG(pred == nullptr || pred_bytes == 8 || pred_bytes == 4 || pred_bytes == 2 || pred_bytes == 1);
-  SEA_CHECK_ARG(!(pred && pred_bytes == 1 && C > 255) && !(pred && pred_bytes == 2 && C > 32767));
-  SEA_CHECK_ARG(!(y_bytes == 1 && C > 255));
-  SEA_CHECK_ARG(workspace_bytes >= sea_loss_workspace_bytes(B, HW));
-  SEA_CHECK_ARG((((uintptr_t)workspace) & 15) == 0);
-  LossArgs a{logits, y, y_bytes, w, mode, track_mode, B, C, HW, grad_scale, dlogits, pred, pred_bytes,
-             loss_px, (BlockPartial*)workspace, (hipStream_t)stream, force_vec};
-  int tiles = 0, rc;
-  switch (dtype) {
-    case SEA_DTYPE_F32: rc = dispatch_dtype<float>(a, layout, &tiles); break;
-    case SEA_DTYPE_BF16: rc = dispatch_dtype<__hip_bfloat16>(a, layout, &tiles); break;
-    case SEA_DTYPE_F16: rc = dispatch_dtype<__half>(a, layout, &tiles); break;
-    default: return SEA_ERR_ARG;
-  }
-  if (rc) return rc;
-  if (!deferred)
-    hipLaunchKernelGGL(loss_finalize, dim3(B), dim3(256), 0, a.s, (const BlockPartial*)workspace, tiles, loss_sum,
-                       track_sum, n_correct);
-  SEA_RETURN_LAST();
-}
+static int elem_bytes_of(int dtype) { return dtype == SEA_DTYPE_F32 ? 4 : (dtype == SEA_DTYPE_BF16 || dtype == SEA_DTYPE_F16) ? 2 : 0; }
 
 }  // namespace sea
 
@@ -590,22 +427,62 @@ extern "C" size_t sea_loss_workspace_bytes(int B, int64_t HW) {
   return ((size_t)B * (size_t)max_tiles(HW) + 1) * sizeof(BlockPartial);
 }
 
+// check the arguments, plan, launch the plan, finalize.  `variant`: a SEA_K2_* word that pins a kernel (tests, A/B runs)
+extern "C" int sea_loss_fwd_bwd_tuned(const void* logits, int dtype, int layout, const void* y, int y_bytes,
+                                      const float* w, int mode, int track_mode, int B, int C, int64_t HW,
+                                      float grad_scale, void* dlogits, void* pred, int pred_bytes, float* loss_px,
+                                      void* workspace, size_t workspace_bytes, float* loss_sum, float* track_sum,
+                                      int32_t* n_correct, void* stream, int variant) {
+  SEA_CHECK_ARG(logits && y && workspace);
+  // loss_sum == track_sum == n_correct == NULL: leave the per-block records in the workspace for
+  // sea_apgd_track (one launch less in the APGD loop)
+  const bool deferred = !loss_sum && !track_sum && !n_correct;
+  SEA_CHECK_ARG(deferred || (loss_sum && track_sum && n_correct));
+  SEA_CHECK_ARG(B > 0 && B <= 65535 && C > 0 && HW > 0);
+  SEA_CHECK_ARG(mode >= 0 && mode <= 3 && track_mode >= 0 && track_mode <= 3);
+  SEA_CHECK_ARG(!((mode == SEA_MODE_MASK_CE_BAL || track_mode == SEA_MODE_MASK_CE_BAL) && w == nullptr));
+  SEA_CHECK_ARG(y_bytes == 8 || y_bytes == 4 || y_bytes == 2 || y_bytes == 1);
+  SEA_CHECK_ARG(pred == nullptr || pred_bytes == 8 || pred_bytes == 4 || pred_bytes == 2 || pred_bytes == 1);
+  SEA_CHECK_ARG(!(pred && pred_bytes == 1 && C > 255) && !(pred && pred_bytes == 2 && C > 32767));
+  SEA_CHECK_ARG(!(y_bytes == 1 && C > 255));
+  SEA_CHECK_ARG(workspace_bytes >= sea_loss_workspace_bytes(B, HW));
+  SEA_CHECK_ARG((((uintptr_t)workspace) & 15) == 0);
+  LossPlan plan;
+  int rc = loss_plan(LossQuery{elem_bytes_of(dtype), layout, C, HW, dlogits != nullptr, (uintptr_t)logits,
+                               (uintptr_t)dlogits, (unsigned)variant}, &plan);
+  if (rc) return rc;
+  const LossArgs a{logits, y, y_bytes, w, mode, track_mode, B, C, HW, grad_scale, dlogits, pred, pred_bytes,
+                   loss_px, (BlockPartial*)workspace, (hipStream_t)stream};
+  switch (dtype) {
+    case SEA_DTYPE_F32: rc = launch<float>(a, plan); break;
+    case SEA_DTYPE_BF16: rc = launch<__hip_bfloat16>(a, plan); break;
+    default: rc = launch<__half>(a, plan); break;
+  }
+  if (rc) return rc;
+  if (!deferred)
+    hipLaunchKernelGGL(loss_finalize, dim3(B), dim3(256), 0, a.s, (const BlockPartial*)workspace, plan.tiles, loss_sum,
+                       track_sum, n_correct);
+  SEA_RETURN_LAST();
+}
+
 extern "C" int sea_loss_fwd_bwd(const void* logits, int dtype, int layout, const void* y, int y_bytes,
                                 const float* w, int mode, int track_mode, int B, int C, int64_t HW,
                                 float grad_scale, void* dlogits, void* pred, int pred_bytes, float* loss_px,
                                 void* workspace, size_t workspace_bytes, float* loss_sum, float* track_sum, int32_t* n_correct,
                                 void* stream) {
-  return loss_fwd_bwd_impl(logits, dtype, layout, y, y_bytes, w, mode, track_mode, B, C, HW, grad_scale, dlogits,
-                           pred, pred_bytes, loss_px, workspace, workspace_bytes, loss_sum, track_sum, n_correct, stream, 0);
+  return sea_loss_fwd_bwd_tuned(logits, dtype, layout, y, y_bytes, w, mode, track_mode, B, C, HW, grad_scale, dlogits, pred,
+                                pred_bytes, loss_px, workspace, workspace_bytes, loss_sum, track_sum, n_correct, stream,
+                                SEA_K2_VARIANT_DEFAULT);
 }
 
-// benchmark hook: same as sea_loss_fwd_bwd but pins the pixels-per-lane of the register kernel
-extern "C" int sea_loss_fwd_bwd_tuned(const void* logits, int dtype, int layout, const void* y, int y_bytes,
-                                      const float* w, int mode, int track_mode, int B, int C, int64_t HW,
-                                      float grad_scale, void* dlogits, void* pred, int pred_bytes, float* loss_px,
-                                      void* workspace, size_t workspace_bytes, float* loss_sum, float* track_sum,
-                                      int32_t* n_correct, void* stream, int force_vec) {
-  return loss_fwd_bwd_impl(logits, dtype, layout, y, y_bytes, w, mode, track_mode, B, C, HW, grad_scale, dlogits,
-                           pred, pred_bytes, loss_px, workspace, workspace_bytes, loss_sum, track_sum, n_correct, stream,
-                           force_vec);
+// host only: the plan of a call, without the call
+extern "C" int sea_loss_plan(int dtype, int layout, int C, int64_t HW, int want_grad, size_t logits_addr,
+                             size_t dlogits_addr, unsigned variant, int32_t out[8]) {
+  SEA_CHECK_ARG(out != nullptr);
+  LossPlan p;
+  const int rc = loss_plan(LossQuery{elem_bytes_of(dtype), layout, C, HW, want_grad != 0, logits_addr, dlogits_addr,
+                                     variant}, &p);
+  const int v[8] = {p.kernel, p.cpad, p.exact, p.vec, p.tune, p.ch, p.waves, p.tiles};
+  for (int i = 0; i < 8; ++i) out[i] = v[i];
+  return rc;
 }

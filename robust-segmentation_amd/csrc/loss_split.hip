@@ -191,45 +191,19 @@ __global__ __launch_bounds__(256, WAVES) void loss_nchw_split(const T* __restric
   block_reduce_store(lsum, tsum, ncorr, partials);
 }
 
+// Launch only: the plan (loss_plan.h) has checked shape, alignment and the 32-bit lane offsets; one wave count per element size
 template <typename T>
-bool dispatch_split(const LossArgs& a, int* tiles_used) {
-  constexpr int PPW = Word<T>::PPW;
-  if (!a.dlogits || (a.C != 150 && a.C != 151) || (a.HW % PPW) != 0) return false;
-  if ((((uintptr_t)a.logits) | ((uintptr_t)a.dlogits)) & 3) return false;
-  if ((int64_t)a.C * a.HW * (int64_t)sizeof(T) >= (int64_t)1 << 31) return false;  // 32-bit lane offsets
-  const int64_t cols = a.HW / PPW;
-  const int tiles = (int)((cols + 127) / 128);
-  dim3 grid(tiles, a.B), block(256);
-  // waves per SIMD asked of the compiler.  Measured cold (tools/k2_lab.py, 8 x 151 x 512 x 512): fp32 4 waves 464 us
-  // (3: 464, 5: 470; register kernel 485); bf16 3 waves 256 us (4 and 5 spill: 430 / 551 us; register kernel 293).
-  // variant (A/B runs): 1 = 5 waves, 2 = 3 waves, 3 = 4 waves
-  int variant = (a.force_vec >> 8) & 15;
-  if (variant == 0) variant = sizeof(T) == 2 ? 2 : 3;
-#define SEA_SPLIT(CC, WV)                                                                                          \
-  hipLaunchKernelGGL((loss_nchw_split<T, CC, WV>), grid, block, 0, a.s, (const T*)a.logits, a.y, a.y_bytes, a.w,  \
-                     a.mode, a.track_mode, a.HW, a.gscale, (T*)a.dlogits, a.pred, a.pred_bytes, a.loss_px, a.partials)
-  if (a.C == 151) {
-    if (variant == 1)
-      SEA_SPLIT(151, 5);
-    else if (variant == 2)
-      SEA_SPLIT(151, 3);
-    else
-      SEA_SPLIT(151, 4);
-  } else {
-    if (variant == 1)
-      SEA_SPLIT(150, 5);
-    else if (variant == 2)
-      SEA_SPLIT(150, 3);
-    else
-      SEA_SPLIT(150, 4);
-  }
-#undef SEA_SPLIT
-  *tiles_used = tiles;
-  return true;
+int launch_split(const LossArgs& a, const LossPlan& p) {
+  constexpr int WAVES = sizeof(T) == 4 ? 4 : 3;
+  auto k = p.cpad == 151 ? loss_nchw_split<T, 151, WAVES> : loss_nchw_split<T, 150, WAVES>;
+  if (p.cpad != 150 && p.cpad != 151) return SEA_ERR_ARG;
+  hipLaunchKernelGGL(k, dim3(p.tiles, a.B), dim3(256), 0, a.s, (const T*)a.logits, a.y, a.y_bytes, a.w, a.mode, a.track_mode,
+                     a.HW, a.gscale, (T*)a.dlogits, a.pred, a.pred_bytes, a.loss_px, a.partials);
+  return 0;
 }
 
-template bool dispatch_split<float>(const LossArgs&, int*);
-template bool dispatch_split<__hip_bfloat16>(const LossArgs&, int*);
-template bool dispatch_split<__half>(const LossArgs&, int*);
+template int launch_split<float>(const LossArgs&, const LossPlan&);
+template int launch_split<__hip_bfloat16>(const LossArgs&, const LossPlan&);
+template int launch_split<__half>(const LossArgs&, const LossPlan&);
 
 }  // namespace sea

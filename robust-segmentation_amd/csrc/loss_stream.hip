@@ -156,31 +156,27 @@ __global__ __launch_bounds__(256, WAVES) void loss_nchw_fwd(const T* __restrict_
   block_reduce_store(lsum, tsum, ncorr, partials);
 }
 
-// streaming no-gradient kernel; variant: 0 = default, 1..3 = alternatives kept for A/B runs (tools/kernel_bench.py)
+// Launch only: (ch, waves) and the grid come from the plan (loss_plan.h)
 template <typename T>
-void launch_fwd(const LossArgs& a, int variant) {
-  constexpr int VEC = 16 / (int)sizeof(T);
-  dim3 grid(tiles_for(a.HW, VEC), a.B), block(256);
-#define SEA_FWD(CH, WV)                                                                                          \
-  hipLaunchKernelGGL((loss_nchw_fwd<T, CH, WV>), grid, block, 0, a.s, (const T*)a.logits, a.y, a.y_bytes, a.w,   \
-                     a.mode, a.track_mode, a.C, a.HW, a.pred, a.pred_bytes, a.loss_px, a.partials)
-  if (variant == 1)
+int launch_fwd(const LossArgs& a, const LossPlan& p) {
+#define SEA_FWD(CH, WV)                                                                                                  \
+  case CH * 16 + WV:                                                                                                     \
+    hipLaunchKernelGGL((loss_nchw_fwd<T, CH, WV>), dim3(p.tiles, a.B), dim3(256), 0, a.s, (const T*)a.logits, a.y,       \
+                       a.y_bytes, a.w, a.mode, a.track_mode, a.C, a.HW, a.pred, a.pred_bytes, a.loss_px, a.partials);    \
+    return 0
+  switch (p.ch * 16 + p.waves) {
     SEA_FWD(4, 5);
-  else if (variant == 2)
     SEA_FWD(8, 3);
-  else if (variant == 3)
     SEA_FWD(6, 4);
-  else if (variant == 4)
     SEA_FWD(2, 8);
-  else if (sizeof(T) == 4)
-    SEA_FWD(4, 5);   // 93 VGPRs, 5 waves/SIMD
-  else
-    SEA_FWD(4, 4);   // 16-bit: 8 pixels per lane, 127 VGPRs
+    SEA_FWD(4, 4);
+  }
 #undef SEA_FWD
+  return SEA_ERR_ARG;
 }
 
-template void launch_fwd<float>(const LossArgs&, int);
-template void launch_fwd<__hip_bfloat16>(const LossArgs&, int);
-template void launch_fwd<__half>(const LossArgs&, int);
+template int launch_fwd<float>(const LossArgs&, const LossPlan&);
+template int launch_fwd<__hip_bfloat16>(const LossArgs&, const LossPlan&);
+template int launch_fwd<__half>(const LossArgs&, const LossPlan&);
 
 }  // namespace sea

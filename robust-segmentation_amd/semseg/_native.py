@@ -37,6 +37,7 @@ _SIGS = {
                               _vp, _vp, _vp, _vp]),
     "sea_loss_fwd_bwd_tuned": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i64, _f, _vp, _vp, _i, _vp, _vp,
                                     _sz, _vp, _vp, _vp, _vp, _i]),
+    "sea_loss_plan": (_i, [_i, _i, _i, _i64, _i, _sz, _sz, _u, C.POINTER(C.c_int32)]),
     "sea_loss_upsampled_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "sea_loss_fwd_bwd_upsampled": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp, _sz, _vp,
                                         _vp, _vp, _i, _vp]),
@@ -172,7 +173,7 @@ def _stream() -> int:
 
 
 # A/B knob for in-loop measurements: SEA_K2_FORCE=<int> is passed as `force_vec` to every K2 launch that does not set
-# one itself (bits 4-7: tuning variant, see csrc/loss_kernels.hip)
+# one itself (a word of `k2_variant`)
 _K2_FORCE = int(os.environ.get("SEA_K2_FORCE", "0"), 0)
 
 
@@ -262,11 +263,33 @@ def loss_workspace(B: int, HW: int, device) -> torch.Tensor:
     return torch.empty(n, dtype=torch.uint8, device=device)
 
 
+K2_VEC_MASK, K2_TUNE_SHIFT, K2_STREAM_SHIFT, K2_NO_SPLIT, K2_REG_ONLY = 0xF, 4, 8, 15 << 8, 0x1000   # SEA_K2_* of sea_hip.h
+K2_KERNELS = ("reg", "stream_grad", "fwd", "split", "nhwc")
+
+
+def k2_variant(vec: int = 0, tune: int = 0, stream: int = 0, reg_only: bool = False) -> int:
+    """The word that pins a K2 kernel (``force_vec`` of ``loss_fwd_bwd``; fields: SEA_K2_* of sea_hip.h): ``vec`` pixels per
+    lane, ``tune`` 2 | 6 | 7 | 15 = none, ``stream`` 1..4 | 15 = no split kernel, ``reg_only``.  All zero: the shipped choice."""
+    if vec not in (0, 1, 2, 4) or tune not in (0, 2, 6, 7, 15) or stream not in (0, 1, 2, 3, 4, 15):
+        raise ValueError(f"no K2 kernel for vec={vec} tune={tune} stream={stream}")
+    return vec | (tune << K2_TUNE_SHIFT) | (stream << K2_STREAM_SHIFT) | (K2_REG_ONLY if reg_only else 0)
+
+
+def loss_plan(dtype, layout: int, C_: int, HW: int, want_grad: bool, logits_addr: int = 0, dlogits_addr: int = 0,
+              variant: int = 0) -> dict:
+    """Which kernel ``loss_fwd_bwd`` runs for these arguments (host only, no device; csrc/loss_plan.h): dict(rc, kernel,
+    cpad, exact, vec, tune, ch, waves, tiles), ``rc`` = 1 where the call itself would be an invalid argument."""
+    out = (C.c_int32 * 8)()
+    rc = lib().sea_loss_plan(DTYPE_CODE[dtype], layout, C_, HW, int(bool(want_grad)), logits_addr, dlogits_addr, variant, out)
+    plan = dict(zip(("kernel", "cpad", "exact", "vec", "tune", "ch", "waves", "tiles"), out), rc=rc)
+    return dict(plan, kernel=K2_KERNELS[plan["kernel"]], exact=bool(plan["exact"]))
+
+
 def loss_fwd_bwd(logits, y, weights, mode: int, track_mode: int, grad_scale: float, want_grad: bool = True,
                  pred=None, loss_px=None, workspace=None, out=None, dlogits=None, force_vec: int = 0,
                  defer: bool = False):
     """Run K2.  Returns dict(dlogits, loss_sum, track_sum, n_correct, pred, workspace).  With ``defer`` the
-    second reduction stage is left to ``apgd_track`` (the sums are then None)."""
+    second reduction stage is left to ``apgd_track`` (the sums are then None).  ``force_vec``: a ``k2_variant`` word."""
     _dev(logits, y, weights, pred, loss_px)
     logits, layout = logits_layout(logits)
     B, Cc, H, W = logits.shape

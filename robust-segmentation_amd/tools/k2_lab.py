@@ -70,11 +70,13 @@ def run_case(C, dtype, grad, variants, rounds=9, hot=False):
     out = []
     for k, v in ts.items():
         ms = sorted(v)[len(v) // 2]
-        out.append(dict(kernel=f"K2 B={B} C={C} {str(dtype)[6:]} {'+grad' if grad else 'no-grad'} [{k}]", state="hot" if hot else "cold",
+        lg, _, dl = sets[0]
+        plan = N.loss_plan(dtype, N.LAYOUT_NCHW, C, HW, grad, lg.data_ptr(), dl.data_ptr() if grad else 0, variants[k])
+        out.append(dict(kernel=f"K2 B={B} C={C} {str(dtype)[6:]} {'+grad' if grad else 'no-grad'} [{k}]", state="hot" if hot else "cold", plan=plan,
                         ms=ms, min_ms=min(v), algorithmic_MB=alg / 1e6, moved_MB=moved / 1e6,
                         frac_8TBps_algorithmic=alg / (ms * 1e-3) / 1e9 / PEAK, frac_8TBps_moved=moved / (ms * 1e-3) / 1e9 / PEAK))
         print(f"{out[-1]['kernel']:64s} {out[-1]['state']:4s} {ms * 1e3:8.1f} us  alg {out[-1]['frac_8TBps_algorithmic']:6.1%}"
-              f"  moved {out[-1]['frac_8TBps_moved']:6.1%} of 8 TB/s", flush=True)
+              f"  moved {out[-1]['frac_8TBps_moved']:6.1%} of 8 TB/s  {plan['kernel']} vec{plan['vec']} tune{plan['tune']}", flush=True)
     return out
 
 
@@ -90,7 +92,6 @@ def main():
     global B
     B = args.batch
     N.lib()
-    LEG = 0x1000
     res = []
     # copy / read ceilings with the library's own probes (1 GiB, cold by size)
     src = torch.empty(256 * 2 ** 20, dtype=torch.float32, device="cuda").normal_()
@@ -125,16 +126,16 @@ def main():
         for dn in args.dtypes:
             dtype = getattr(torch, dn)
             # no gradient: streaming variants vs the legacy register kernel
-            v = {"default": 0, "stream CH4/5w": 0x100, "stream CH8/3w": 0x200, "stream CH6/4w": 0x300,
-                 "stream CH2/8w": 0x400, "register kernel": LEG, "register kernel untuned": LEG | (15 << 4)}
+            v = {"default": 0, "stream CH4/5w": N.k2_variant(stream=1), "stream CH8/3w": N.k2_variant(stream=2),
+                 "stream CH6/4w": N.k2_variant(stream=3), "stream CH2/8w": N.k2_variant(stream=4),
+                 "register kernel": N.k2_variant(reg_only=True), "register kernel untuned": N.k2_variant(tune=15, reg_only=True)}
             if args.defaults_only:
                 v = {"default": 0}
             for hot in ([False, True] if args.hot else [False]):
                 res += run_case(C, dtype, False, v, hot=hot)
             # with gradient
-            v = {"default": 0, "register kernel": LEG, "register kernel untuned": LEG | (15 << 4)}
-            if C in (150, 151):
-                v.update({"split 5 waves": 0x100, "split 3 waves": 0x200, "split 4 waves": 0x300})
+            v = {"default": 0, "register kernel": N.k2_variant(reg_only=True),
+                 "register kernel untuned": N.k2_variant(tune=15, reg_only=True)}
             if args.defaults_only:
                 v = {"default": 0}
             for hot in ([False, True] if args.hot else [False]):

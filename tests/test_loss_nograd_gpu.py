@@ -11,8 +11,8 @@ Bars (head of test_kernels_gpu.py and its golden test): pred and n_correct exact
 rtol 3e-5, atol 1e-6; loss_px rtol 2e-5, atol 2e-6; the same for 16-bit logits (the kernels compute in fp32 from the same
 rounded inputs).  Every launch runs twice and the two results are equal bit for bit (fixed-order reductions).
 
-Which kernel a case reaches (dispatch_dtype / dispatch_nchw / launch_nhwc of csrc/loss_kernels.hip, launch_fwd of
-csrc/loss_stream.hip).  "even" = 48 x 52 = 2496 pixels, a multiple of 8: three tiles of 1024 pixels at four pixels per lane,
+Which kernel a case reaches (loss_plan of csrc/loss_plan.h; tests/test_loss_plan_cpu.py pins these rows without a device;
+force_vec is a word of _native.k2_variant).  "even" = 48 x 52 = 2496 pixels, a multiple of 8: three tiles of 1024 pixels at four pixels per lane,
 two of 2048 at eight, the last one ragged; "odd" = 47 x 53 = 2491 pixels: one pixel per lane, no 16-byte plane alignment.
 
   layout  H*W   C / force_vec                      kernel
