@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """PIR-AT outer step as BASELINE configs[3] writes it: UperNet-ConvNeXt-S, ADE20K-shaped (C=151), 5-step CE PGD
-inner attack, batch 8 per GPU, fp32 vs bf16 autocast.   python devtools/pirat_bench.py"""
+inner attack, batch 8 per GPU, fp32 vs bf16 autocast.   python devtools/pirat_bench.py [--native-blocks ...]
+(arguments are handed on to tools.train_rob_seg; PIRAT_MODE=fp32|bf16 picks one mode)"""
 import json
 import os
 import sys
@@ -21,4 +22,4 @@ yaml.safe_dump(cfg, open(td + "/cfg.yaml", "w"))
 modes = {"fp32": [[]], "bf16": [["--bf16"]]}.get(os.environ.get("PIRAT_MODE", ""), [[], ["--bf16"]])
 for flags in modes:
     out = td + "/o.json"
-    train_rob_seg.main(["--cfg", td + "/cfg.yaml", "--synthetic", "16", "--steps", "6", "--warmup", "2", "--batch_size", "8", "--json", out] + flags)
+    train_rob_seg.main(["--cfg", td + "/cfg.yaml", "--synthetic", "16", "--steps", "6", "--warmup", "2", "--batch_size", "8", "--json", out] + flags + sys.argv[1:])

@@ -349,6 +349,32 @@ int sea_layernorm_fwd(const float* x, const float* w, const float* b, float* y, 
 int sea_layernorm_bwd(const float* g, const float* x, const float* w, const float* mean, const float* rstd,
                       float* dx, int64_t rows, int C, void* stream);
 
+/* T3a (model side, training) sea_layernorm_bwd with trainable affine parameters (convnext_orig.py:19-40): dx, bit for bit
+ * sea_layernorm_bwd's (one kernel source, one translation unit), plus dw[c] = sum_r g[r,c] * xhat[r,c] and
+ * db[c] = sum_r g[r,c], xhat = (x - mean) * rstd.  Deterministic two-stage sum, no float atomics, grid a function of
+ * (rows, C) only: a thread adds its rows in increasing index (dw: one fma per row), a block combines its row groups
+ * through LDS in slot order into one partial row of `ws` (sea_layernorm_bwd_params_workspace(rows, C) floats, 16-byte
+ * aligned), then the blocks are added in index order, associated as a balanced binary tree (adjacent blocks first: a
+ * left-to-right walk over up to 1024 partial rows would round 1024 times at the magnitude of the total).  Same contract as M5: C % 4 == 0, C <= 1024, 16-byte alignment. */
+int64_t sea_layernorm_bwd_params_workspace(int64_t rows, int C);
+int sea_layernorm_bwd_params(const float* g, const float* x, const float* w, const float* mean, const float* rstd,
+                             float* dx, float* dw, float* db, float* ws, int64_t rows, int C, void* stream);
+
+/* T3b (model side, training) the tail of a ConvNeXt block on dense NHWC rows (convnext_orig.py:75-86: layer scale,
+ * stochastic depth, residual add), rows = B * HW < 2^31, one streaming pass with 16-byte accesses per direction:
+ *   forward :  out[r,c] = x[r,c] + (y[r,c] * gamma[c]) * s[r / HW]        (two rounded products, then the add)
+ *   backward:  t = g[r,c] * s[r / HW];  gy[r,c] = t * gamma[c];  ggamma[c] = sum_r t * y[r,c]  (gx = g: no kernel)
+ * s (B): 0 or 1 / keep per image, NULL = 1; gamma (C) or NULL = 1.  No special case for a dropped image: s = 0 multiplies.
+ * ggamma (NULL: not computed; else y and `ws`, sea_block_tail_bwd_workspace(rows, C) floats, are required and gy may be
+ * NULL) by the two-stage sum of T3a: per thread rows in increasing index by one fma each, row groups of a block through
+ * LDS in slot order, blocks in index order as a balanced binary tree.  No float atomics; bitwise reproducible.  C % 4 == 0, C <= 1024, 16-byte
+ * alignment of the row tensors, gamma and ws. */
+int sea_block_tail_fwd(const float* x, const float* y, const float* gamma, const float* s, float* out, int64_t rows, int HW,
+                       int C, void* stream);
+int64_t sea_block_tail_bwd_workspace(int64_t rows, int C);
+int sea_block_tail_bwd(const float* g, const float* y, const float* gamma, const float* s, float* gy, float* ggamma, float* ws,
+                       int64_t rows, int HW, int C, void* stream);
+
 /* M1w (model side, training) weight and bias gradient of the NHWC depthwise 7x7: gw (C,7,7), gb (C) or NULL from x and gy
  * (B,H,W,C) dense fp32 (PIR-AT's outer backward; convnext_orig.py:55-57).  Deterministic two-pass sum (per-tile partial
  * sums in `ws`, sea_dwconv7x7_nhwc_wgrad_workspace(B, C, H) floats, then the tiles in index order).  C % 4 == 0. */

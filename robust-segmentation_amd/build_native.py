@@ -38,6 +38,7 @@ SOURCES = [
     ("transpose_kernels.hip", ["-ffp-contract=off"]),
     ("wino_kernels.hip", []),
     ("ln_kernels.hip", []),
+    ("block_tail.hip", ["-ffp-contract=off"]),
     ("stem_kernels.hip", []),
     ("fpn_fused.hip", []),
     ("probe_kernels.hip", []),
@@ -55,7 +56,7 @@ SOURCES = [
     ("greedy_host.cpp", ["-ffp-contract=off"]),
     ("api_misc.cpp", []),
 ]
-HEADERS = ["sea_common.h", "loss_common.h", "loss_plan.h", "gemm_split.h", "bilinear_map.h", os.path.join("..", "..", "include", "sea_hip.h")]
+HEADERS = ["sea_common.h", "colsum.h", "loss_common.h", "loss_plan.h", "gemm_split.h", "bilinear_map.h", os.path.join("..", "..", "include", "sea_hip.h")]
 
 
 def _hipcc() -> str:

@@ -60,6 +60,11 @@ _SIGS = {
     "sea_upsample_bilinear_bwd": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "sea_layernorm_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _f, _vp]),
     "sea_layernorm_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _vp]),
+    "sea_layernorm_bwd_params_workspace": (_i64, [_i64, _i]),
+    "sea_layernorm_bwd_params": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _vp]),
+    "sea_block_tail_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _vp]),
+    "sea_block_tail_bwd_workspace": (_i64, [_i64, _i]),
+    "sea_block_tail_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _vp]),
     "sea_dwconv7x7_nhwc_wgrad_workspace": (_i64, [_i, _i, _i]),
     "sea_dwconv7x7_nhwc_wgrad": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "sea_adaptive_avg_pool_nhwc_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
@@ -897,6 +902,63 @@ def layernorm_backward(g, x, weight, mean, rstd):
     _check(lib().sea_layernorm_bwd(_p(_f32c(g)), _p(_f32c(x)), _p(_f32c(weight)), _p(mean), _p(rstd), _p(dx),
                                    x.numel() // Cc, Cc, _stream()), "sea_layernorm_bwd")
     return dx
+
+
+# ------------------------------------------------------------------------------------------------ T3
+def layernorm_backward_params(g, x, weight, mean, rstd):
+    """(dx, dw, db) of ``layernorm`` with trainable weight / bias: dx has ``layernorm_backward``'s bits, dw / db are
+    deterministic two-stage sums (include/sea_hip.h T3a)"""
+    _dev(g, x, weight, mean, rstd)
+    Cc = x.shape[-1]
+    rows = x.numel() // Cc
+    L = lib()
+    ws = torch.empty(int(L.sea_layernorm_bwd_params_workspace(rows, Cc)), dtype=torch.float32, device=x.device)
+    dx = torch.empty_like(x)
+    dw = torch.empty(Cc, dtype=torch.float32, device=x.device)
+    db = torch.empty(Cc, dtype=torch.float32, device=x.device)
+    _check(L.sea_layernorm_bwd_params(_p(_f32c(g)), _p(_f32c(x)), _p(_f32c(weight)), _p(mean), _p(rstd), _p(dx), _p(dw),
+                                      _p(db), _p(ws), rows, Cc, _stream()), "sea_layernorm_bwd_params")
+    return dx, dw, db
+
+
+def _tail_args(x, y, gamma, s, what):
+    if x.dim() != 4 or y.shape != x.shape or x.shape[-1] % 4 or x.shape[-1] > 1024 or x.numel() == 0:
+        raise SeaNativeError(f"{what}: two (B,H,W,C) tensors of one shape, C % 4 == 0, C <= 1024")
+    B, H, W, Cc = x.shape
+    if gamma is not None and _f32c(gamma).shape != (Cc,):
+        raise SeaNativeError(f"{what}: gamma must be (C)")
+    if s is not None and _f32c(s).numel() != B:
+        raise SeaNativeError(f"{what}: s must hold one factor per image")
+    return B * H * W, H * W, Cc
+
+
+def block_tail(x, y, gamma=None, s=None):
+    """x + (y * gamma) * s on (B,H,W,C) contiguous fp32 tensors: layer scale, stochastic depth and residual add of a ConvNeXt
+    block in one pass.  gamma (C) or None; s: B per-image factors (0 or 1 / keep) or None (include/sea_hip.h T3b)"""
+    _dev(x, y, gamma, s)
+    rows, HW, Cc = _tail_args(x, y, gamma, s, "block_tail")
+    out = torch.empty_like(x)
+    _check(lib().sea_block_tail_fwd(_p(_f32c(x)), _p(_f32c(y)), _p(gamma), _p(s), _p(out), rows, HW, Cc, _stream()),
+           "sea_block_tail_fwd")
+    return out
+
+
+def block_tail_backward(g, y, gamma=None, s=None, want_gamma: bool = False):
+    """(gy, ggamma or None) of ``block_tail`` given g = d loss / d out (the gradient of x is g itself); ``y`` may be None
+    unless ``want_gamma``"""
+    _dev(g, y, gamma, s)
+    rows, HW, Cc = _tail_args(g, g if y is None else y, gamma, s, "block_tail_backward")
+    L = lib()
+    gy = torch.empty_like(g)
+    gg = ws = None
+    if want_gamma:
+        if y is None:
+            raise SeaNativeError("block_tail_backward: the layer-scale gradient needs y")
+        ws = torch.empty(int(L.sea_block_tail_bwd_workspace(rows, Cc)), dtype=torch.float32, device=g.device)
+        gg = torch.empty(Cc, dtype=torch.float32, device=g.device)
+    _check(L.sea_block_tail_bwd(_p(_f32c(g)), _p(None if y is None else _f32c(y)), _p(gamma), _p(s), _p(gy), _p(gg), _p(ws),
+                                rows, HW, Cc, _stream()), "sea_block_tail_bwd")
+    return gy, gg
 
 
 # ------------------------------------------------------------------------------------------------ M2''

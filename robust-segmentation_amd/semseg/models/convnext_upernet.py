@@ -80,11 +80,41 @@ class _LayerNormHip(torch.autograd.Function):
         return N.layernorm_backward(g.contiguous(), x, weight, mean, rstd), None, None, None
 
 
+# T3 (training, off by default): the train-mode ConvNeXt block stays in NHWC on libsea_hip -- every LayerNorm with trainable
+# weight / bias takes M5's forward and T3a's backward (dx, dw, db), and Block.forward gets a branch for any drop rate
+# (depthwise M1 / M1w, T3a, the fused layer-scale / stochastic-depth / residual tail T3b).  fp32 only.
+TRAIN_NATIVE_BLOCKS = os.environ.get("SEA_TRAIN_BLOCKS", "0") not in ("", "0")
+
+
+class _LayerNormHipTrain(torch.autograd.Function):
+    """LayerNorm over the last dim with trainable affine parameters: M5's forward (the bits of the frozen path), T3a's
+    backward (input gradient with M5's bits, weight / bias gradients by a deterministic two-stage sum)."""
+
+    @staticmethod
+    @_fp32_fwd
+    def forward(ctx, x, weight, bias, eps):
+        from .. import _native as N
+        y, mean, rstd = N.layernorm(x, weight, bias, eps)
+        ctx.save_for_backward(x, weight, mean, rstd)
+        return y
+
+    @staticmethod
+    @_fp32_bwd
+    def backward(ctx, g):
+        from .. import _native as N
+        x, weight, mean, rstd = ctx.saved_tensors
+        dx, dw, db = N.layernorm_backward_params(g.contiguous(), x, weight, mean, rstd)
+        return dx, dw, db, None
+
+
 def _layer_norm(x, dim, weight, bias, eps):
     if (USE_HIP_LAYERNORM and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and dim % 4 == 0
-            and dim <= 1024 and x.shape[-1] == dim and not weight.requires_grad and not bias.requires_grad):
+            and dim <= 1024 and x.shape[-1] == dim):
         # also under autocast: LayerNorm is an fp32 op there too, and the kernel is called with raw fp32 pointers
-        return _LayerNormHip.apply(x, weight, bias, eps)
+        if not weight.requires_grad and not bias.requires_grad:
+            return _LayerNormHip.apply(x, weight, bias, eps)
+        if TRAIN_NATIVE_BLOCKS and weight.dtype == torch.float32 and bias.dtype == torch.float32:
+            return _LayerNormHipTrain.apply(x, weight, bias, eps)
     return F.layer_norm(x, (dim,), weight, bias, eps)
 
 
@@ -634,6 +664,33 @@ class _ScaleResidual(torch.autograd.Function):
         return gx, gy, gg
 
 
+class _BlockTail(torch.autograd.Function):
+    """out = x + (y * gamma) * s on (B,H,W,C) rows through libsea_hip T3b: layer scale, stochastic depth (s: B per-image
+    factors, 0 or 1 / keep, or None) and the residual add of a train-mode block in one pass; backward sends g unchanged to
+    the trunk, (g * s) * gamma to the branch, and sums the layer-scale gradient in the same pass when gamma trains."""
+
+    @staticmethod
+    @_fp32_fwd
+    def forward(ctx, x, y, gamma, s):
+        from .. import _native as N
+        y = y.contiguous()
+        ctx.save_for_backward(y if (gamma is not None and gamma.requires_grad) else None, gamma, s)
+        return N.block_tail(x.contiguous(), y, gamma, s)
+
+    @staticmethod
+    @_fp32_bwd
+    def backward(ctx, g):
+        from .. import _native as N
+        y, gamma, s = ctx.saved_tensors
+        g = g.contiguous()
+        gx = g if ctx.needs_input_grad[0] else None
+        gy = gg = None
+        want_gamma = gamma is not None and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1] or want_gamma:
+            gy, gg = N.block_tail_backward(g, y, gamma, s, want_gamma)
+        return gx, gy, gg, None
+
+
 USE_HIP_TRANSPOSE = True
 STAGE_ENTRY_CONTIGUOUS = False  # the trunk arrives channels_last from MIOpen; Block has an all-NHWC path for that
 
@@ -739,6 +796,19 @@ class Block(nn.Module):
         self.drop_path = StochasticDepth(drop_path) if drop_path > 0 else nn.Identity()
 
     def forward(self, x):
+        if (TRAIN_NATIVE_BLOCKS and self.training and USE_HIP_DWCONV and x.is_cuda and x.dtype == torch.float32
+                and self.dwconv.weight.dtype == torch.float32 and x.shape[1] % 4 == 0 and x.shape[1] <= 1024
+                and not x.is_contiguous() and x.is_contiguous(memory_format=torch.channels_last)):
+            # T3: the train-mode block in NHWC for any drop rate (weights train: plain modules for the projections)
+            xn = x.permute(0, 2, 3, 1)
+            xn, y = _DwConv7x7NHWCSkip.apply(xn, self.dwconv.weight, self.dwconv.bias, _taps_major(self.dwconv))
+            y = self.pwconv2(self.act(self.pwconv1(self.norm(y))))
+            s = None
+            if isinstance(self.drop_path, StochasticDepth) and self.drop_path.p != 0.0:
+                # the very call StochasticDepth.forward makes: the generator is consumed as with the switch off
+                keep = 1.0 - self.drop_path.p
+                s = x.new_empty((x.shape[0],) + (1,) * (x.ndim - 1)).bernoulli_(keep) / keep
+            return _BlockTail.apply(xn, y, self.gamma, s).permute(0, 3, 1, 2)
         no_drop = isinstance(self.drop_path, nn.Identity) or not self.training
         if (USE_HIP_DWCONV and no_drop and x.is_cuda and x.dtype == torch.float32 and x.shape[1] % 4 == 0
                 and x.shape[1] <= 1024 and not x.is_contiguous()

@@ -21,6 +21,8 @@ semseg/schedulers.py:80-134.  PSPNet (configs/pascalvoc_pspnet.yaml) follows the
 (tools/train_rob_seg.py:92-98, 185-204, 338-361): ``PSPNet(50, N_CLS)``, loss = main_loss + 0.4 * aux_loss, SGD over eight
 parameter groups (layer0-4, then ppm, cls, aux) and the poly rule set after every step, x10 on the new modules, with no
 warm-up (SCHEDULER is ignored).  Its crops satisfy (H - 1) % 8 == 0.
+``--native-blocks`` runs the fp32 outer step's ConvNeXt trunk in NHWC on libsea_hip for this run (T3: LayerNorm with
+parameter gradients, fused stochastic-depth tail; ``semseg.models.convnext_upernet.TRAIN_NATIVE_BLOCKS``).
 """
 from __future__ import annotations
 
@@ -40,6 +42,7 @@ if _PKG not in sys.path:
     sys.path.insert(0, _PKG)
 
 from semseg import attacker  # noqa: E402
+from semseg.models import convnext_upernet as _convnext  # noqa: E402
 from semseg.models import PSPNet, UperNetForSemanticSegmentation, create_segmenter  # noqa: E402
 from semseg.val import Pgd_Attack, Pgd_Attack_1  # noqa: E402
 
@@ -145,7 +148,12 @@ def _main(argv=None):
     ap.add_argument("--native-criterion", action="store_true",
                     help="Segmenter branch: compute the outer step's criterion with get_loss(cfg LOSS.NAME, -1, None, "
                          "native=True) (T2, csrc/train_loss.hip) instead of F.cross_entropy")
+    ap.add_argument("--native-blocks", action="store_true",
+                    help="ConvNeXt trunk: train-mode blocks and trainable LayerNorms in NHWC on libsea_hip (T3, fp32; "
+                         "csrc/ln_kernels.hip, csrc/block_tail.hip) for this run")
     args = ap.parse_args(argv)
+    if args.native_blocks:
+        _convnext.TRAIN_NATIVE_BLOCKS = True
     with open(args.cfg) as f:
         cfg = yaml.load(f, Loader=yaml.SafeLoader)
     train_cfg, model_cfg, data_cfg = cfg["TRAIN"], cfg["MODEL"], cfg["DATASET"]
@@ -275,6 +283,7 @@ def _main(argv=None):
                "samples_per_s": world * bs * args.steps / dt,
                "inner_image_iterations_per_s": world * bs * args.steps * n_inner / dt,
                "ms_per_outer_step": dt * 1e3 / args.steps, "last_loss": float(loss)}
+        out["native_blocks"] = bool(_convnext.TRAIN_NATIVE_BLOCKS)
         print(json.dumps(out))
         if args.json:
             json.dump(out, open(args.json, "w"))
@@ -285,16 +294,19 @@ def _main(argv=None):
                        args.dump_params)
     if world > 1:
         dist.destroy_process_group()
+    return out if rank == 0 else None
 
 
 def main(argv=None):
-    """`_main` with the process-global switch it sets (MIOpen find mode) restored on exit: a caller that runs this
-    in-process (tests do) must not inherit `cudnn.benchmark = True`."""
-    prev = torch.backends.cudnn.benchmark
+    """`_main` with the process-global switches it sets (MIOpen find mode, ``--native-blocks``) restored on exit: a caller
+    that runs this in-process (tests do) must not inherit `cudnn.benchmark = True` or the T3 switch.  Returns rank 0's
+    result record (the JSON line it prints)."""
+    prev, prev_blocks = torch.backends.cudnn.benchmark, _convnext.TRAIN_NATIVE_BLOCKS
     try:
         return _main(argv)
     finally:
         torch.backends.cudnn.benchmark = prev
+        _convnext.TRAIN_NATIVE_BLOCKS = prev_blocks
 
 
 if __name__ == "__main__":
