@@ -17,14 +17,37 @@
 // The K loop is the ping-pong loop of gemm_split_pp.hip: one barrier per K step, the operand split of the next tile placed by
 // hand between the wave's own MFMAs, buffer loads with a zero-record descriptor past the end of K.  Same split, same MFMA
 // order per accumulator as the other two kernels: the same bits.
+//
+// Between tiles (profiles/r11_gemm_big_stamps.md: per-block time stamps of the diagnostic build below).  A K = 512 tile takes
+// 52.7 us: 3.5 prologue, 38.7 K loop, 10 epilogue, 0.8 until the CU's next block starts.  The C stores cost 4 us of that
+// (knock-out) and only the FIRST round of a launch stores as one burst; from the second round on the CUs have drifted apart
+// by themselves, so spreading the first round in time gains nothing (sweep in the same file) and is not in the product.
 #include "gemm_split.h"
 
 namespace sea {
 
+// -DSEA_GEMM_BIG_DIAG (devtools/gemm_big_stamps.py, its own .so, never the product library): time stamps per block, the
+// knock-outs KO, and a stagger of the first round of blocks: block b < first_round waits (row block % 8) * step_ticks ticks of
+// the 100 MHz clock before its first load, in a loop that reads the clock only and whose trip count is bounded.
+#ifdef SEA_GEMM_BIG_DIAG
+struct BigDiag {
+  int first_round, step_ticks;
+  unsigned long long* stamps;   // 8 words per tile, or null
+};
+#define SEA_BIG_DIAG_PARAM , const BigDiag dg
+#define SEA_BIG_DIAG_ARG , dg
+#define SEA_BIG_STAMP(i) do { if constexpr (STAMP) { __builtin_amdgcn_sched_barrier(0); stamp[i] = __builtin_amdgcn_s_memrealtime(); __builtin_amdgcn_sched_barrier(0); } } while (0)
+#else
+#define SEA_BIG_DIAG_PARAM
+#define SEA_BIG_DIAG_ARG
+#define SEA_BIG_STAMP(i) do {} while (0)
+#endif
+
 // WM x WN waves (WM WN = 8), wave tile 64 x 32 TN; PRO: 0 none, 1 A * GELU'(t), 2 GELU(A), 3 t > 0 ? A : 0
 // DEPTH: register sets of staged loads (2 = a tile's loads are issued two K steps before its split)
-template <bool F16, int WM, int WN, int TN, int PRO, int DEPTH>
-__global__ __launch_bounds__(64 * WM * WN) void gemm_split_big_kernel(const GemmSplitArgs p) {
+// KO / STAMP: timing-only builds of devtools/gemm_big_stamps.py (-DSEA_GEMM_BIG_DIAG); 0 / false in the product
+template <bool F16, int WM, int WN, int TN, int PRO, int DEPTH, int KO = 0, bool STAMP = false>
+__global__ __launch_bounds__(64 * WM * WN) void gemm_split_big_kernel(const GemmSplitArgs p SEA_BIG_DIAG_PARAM) {
   static_assert(WM * WN == 8, "eight waves, two per SIMD");
   constexpr int TERMS = 2;
   constexpr int MI = 2;                                    // 32-row sub-tiles of a wave's 64-row tile
@@ -52,6 +75,17 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_split_big_kernel(const Gemm
   const int mb = t2 % p.mblocks;
   const int g = t2 / p.mblocks;
   const int m0 = mb * BM, n0 = nb * BN;
+#ifdef SEA_GEMM_BIG_DIAG
+  [[maybe_unused]] uint64_t stamp[6] = {};
+  SEA_BIG_STAMP(0);
+  if ((int)blockIdx.x < dg.first_round) {   // (`trips` bounds the loop whatever the clock does; at a shader clock up to 2.5 GHz a trip of 512 cycles is at least 20 ticks, so the clock ends it first)
+    const uint32_t want = (uint32_t)(t2 % 8) * (uint32_t)dg.step_ticks;
+    const uint32_t trips = (want >> 3) + 16;
+    const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+    for (uint32_t it = 0; it < trips && (uint32_t)(__builtin_amdgcn_s_memrealtime() - t0) < want; ++it) __builtin_amdgcn_s_sleep(8);
+  }
+  SEA_BIG_STAMP(1);
+#endif
   const float* const w_inv = F16 ? (const float*)((const char*)p.w_inv + (int64_t)g * p.strideW) : nullptr;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -291,6 +325,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_split_big_kernel(const Gemm
   read_a(st0, 0);
 #pragma unroll
   for (int ni = 0; ni < TN; ++ni) read_b(st0, 0, ni);
+  SEA_BIG_STAMP(2);
   int kb = 0;
   for (; kb + 2 <= nkb; kb += 2) {
     step(st0, st1, RB, kb + 1 + DEPTH);
@@ -298,6 +333,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_split_big_kernel(const Gemm
   }
   if (kb < nkb) step(st0, st1, RB, nkb);
 #undef SEA_PIN
+  SEA_BIG_STAMP(3);
 
   // ---- epilogue: each wave turns its 64 x WT tile through its share of the idle stages, 32 rows at a time, and stores 16
   // bytes per lane along the rows (see gemm_split.h for the 128 x 128 kernels' version)
@@ -322,39 +358,62 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_split_big_kernel(const Gemm
 #pragma unroll
   for (int mi = 0; mi < MI; ++mi) {
     if (mi) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    // the inverse scales of this lane's 16 rows (4 j + 0..3 of ri = rows 8 j + 4 h + 0..3), read BEFORE the scratch is written:
+    // behind a scratch store the compiler has to assume that row_inv changed, and a reload per element is an LDS round trip
+    // per element, 128 in a row per wave (profiles/r11_gemm_big_stamps.md: 8 of a tile's 10 us epilogue were CU-local)
+    f32x4 ri[4] = {};
+    if constexpr (F16) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) ri[j] = *(const f32x4*)(row_inv + (wave_u / WN) * 32 * MI + mi * 32 + 8 * j + 4 * h);
+    }
 #pragma unroll
     for (int ni = 0; ni < TN; ++ni) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const int row_l = (e & 3) + 8 * (e >> 2) + 4 * h;
-        const float v = (F16 ? acc[mi][ni][e] * (row_inv[(wave_u / WN) * 32 * MI + mi * 32 + row_l] * wi_c[ni]) : acc[mi][ni][e]) + bv_c[ni];
+        const float v = (F16 ? acc[mi][ni][e] * (ri[e >> 2][e & 3] * wi_c[ni]) : acc[mi][ni][e]) + bv_c[ni];
         *(float*)(scr + (row_l * WT + ni * 32 + r) * 4) = v;
       }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    // scratch reads in flight per lane (8 / 6 float4 = 32 / 24 VGPRs): one LDS latency per CH stores instead of one per store.
+    // (The 256 x 256 fp16 kernel stands at 254 of 256 VGPRs, the peak being the K loop; the registers used here are dead
+    // K-loop registers.  After any edit of this epilogue check -Rpass-analysis=kernel-resource-usage: a spill lands in the K loop's
+    // allocation as well, and a scratch access there waits behind the refill loads.)
+    constexpr int CH = WT / 16;
 #pragma unroll
-    for (int k = 0; k < WT / 8; ++k) {                  // 32 WT / 4 float4 of the scratch, 64 per trip, in address order
-      const int f = k * 64 + lane;
-      const int row_l = f / F4_ROW, c4 = f - row_l * F4_ROW;
-      f32x4 v = *(const f32x4*)(scr + f * 16);
-      const int row = row0_u + mi * 32 + row_l, col4 = n0 + wn * WT + 4 * c4;
-      if (row >= M || col4 >= N) continue;
-      float* const cp = Cg + (int64_t)row * ldc + col4;
-      if (relu) {
+    for (int k0 = 0; k0 < WT / 8; k0 += CH) {           // 32 WT / 4 float4 of the scratch, 64 per trip, in address order
+      f32x4 vv[CH];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
-      }
-      if (vec) {
-        *(f32x4*)cp = v;
-      } else {
+      for (int j = 0; j < CH; ++j) vv[j] = *(const f32x4*)(scr + ((k0 + j) * 64 + lane) * 16);
 #pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (col4 + e < N) cp[e] = v[e];
-      }
+      for (int j = 0; j < CH; ++j) {
+        const int f = (k0 + j) * 64 + lane;
+        const int row_l = f / F4_ROW, c4 = f - row_l * F4_ROW;
+        f32x4 v = vv[j];
+        const int row = row0_u + mi * 32 + row_l, col4 = n0 + wn * WT + 4 * c4;
+        if (row >= M || col4 >= N) continue;
+        float* const cp = Cg + (int64_t)row * ldc + col4;
+        if (relu) {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const uint32_t vb = (col4 + e < N) ? (__float_as_uint(v[e]) & 0x7fffffffu) : 0u;
-        omax = vb > omax ? vb : omax;
+          for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
+        }
+        if constexpr ((KO & 1) != 0) {   // timing only: no C stores (the test keeps the values live)
+          if (__float_as_uint(v[0]) != 0x7fc12345u) continue;
+        }
+        if (vec) {
+          if constexpr ((KO & 64) != 0) __builtin_nontemporal_store(v, (f32x4*)cp);   // timing only
+          else *(f32x4*)cp = v;
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (col4 + e < N) cp[e] = v[e];
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const uint32_t vb = (col4 + e < N) ? (__float_as_uint(v[e]) & 0x7fffffffu) : 0u;
+          omax = vb > omax ? vb : omax;
+        }
       }
     }
   }
@@ -366,12 +425,26 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_split_big_kernel(const Gemm
     }
     if (lane == 0 && omax > *(volatile uint32_t*)p.out_amax) atomicMax(p.out_amax, omax);
   }
+#ifdef SEA_GEMM_BIG_DIAG
+  if constexpr (STAMP) {   // wave 0's clock (100 MHz): entry, first load, first MFMA, K loop done, stores issued, stores drained
+    SEA_BIG_STAMP(4);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    SEA_BIG_STAMP(5);
+    if (tid == 0) {
+      unsigned long long* const o = dg.stamps + (int64_t)logical * 8;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) o[i] = stamp[i];
+      o[6] = (unsigned long long)__builtin_amdgcn_s_getreg(4 | (31 << 11)) | ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32);   // HW_ID, XCC_ID
+      o[7] = blockIdx.x;
+    }
+  }
+#endif
 }
 
-template <bool F16, int WM, int WN, int TN, int PRO, int DEPTH>
-static void big_launch_one(const GemmSplitArgs& p, hipStream_t st) {
+template <bool F16, int WM, int WN, int TN, int PRO, int DEPTH, int KO = 0, bool STAMP = false>
+static void big_launch_one(const GemmSplitArgs& p SEA_BIG_DIAG_PARAM, hipStream_t st) {
   constexpr int lds = 2 * 65536 + 2 * 64 * WM * (int)sizeof(float);
-  auto k = gemm_split_big_kernel<F16, WM, WN, TN, PRO, DEPTH>;
+  auto k = gemm_split_big_kernel<F16, WM, WN, TN, PRO, DEPTH, KO, STAMP>;
   static bool attr_set_dev[64] = {};
   int dev = 0;
   (void)hipGetDevice(&dev);
@@ -379,7 +452,7 @@ static void big_launch_one(const GemmSplitArgs& p, hipStream_t st) {
     (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     attr_set_dev[dev & 63] = true;
   }
-  hipLaunchKernelGGL(k, dim3(p.per_xcd * 8), dim3(64 * WM * WN), (size_t)lds, st, p);
+  hipLaunchKernelGGL(k, dim3(p.per_xcd * 8), dim3(64 * WM * WN), (size_t)lds, st, p SEA_BIG_DIAG_ARG);
 }
 
 // launches a one-block-per-CU kernel; the caller has checked: terms 22 or 2, no fused epilogue extras.
@@ -396,20 +469,60 @@ bool gemm_split_big_launch(GemmSplitArgs p, int terms, int batch, int shape, int
   p.total = (int)total;
   p.per_xcd = (p.total + 7) / 8;
   const bool f16 = terms == 22;
+#ifdef SEA_GEMM_BIG_DIAG
+  const BigDiag dg = {0, 0, nullptr};
+#endif
   if (shape == 0) {
-    if (f16) big_launch_one<true, 4, 2, 4, 0, 1>(p, st); else big_launch_one<false, 4, 2, 4, 0, 1>(p, st);
+    if (f16) big_launch_one<true, 4, 2, 4, 0, 1>(p SEA_BIG_DIAG_ARG, st); else big_launch_one<false, 4, 2, 4, 0, 1>(p SEA_BIG_DIAG_ARG, st);
     return true;
   }
 #define SEA_BIG_WIDE(F)                                              \
   do {                                                               \
-    if (pro == 0) big_launch_one<F, 2, 4, 3, 0, 2>(p, st);           \
-    else if (pro == 1) big_launch_one<F, 2, 4, 3, 1, 1>(p, st);      \
-    else if (pro == 2) big_launch_one<F, 2, 4, 3, 2, 2>(p, st);      \
-    else big_launch_one<F, 2, 4, 3, 3, 1>(p, st);                    \
+    if (pro == 0) big_launch_one<F, 2, 4, 3, 0, 2>(p SEA_BIG_DIAG_ARG, st);       \
+    else if (pro == 1) big_launch_one<F, 2, 4, 3, 1, 1>(p SEA_BIG_DIAG_ARG, st);  \
+    else if (pro == 2) big_launch_one<F, 2, 4, 3, 2, 2>(p SEA_BIG_DIAG_ARG, st);  \
+    else big_launch_one<F, 2, 4, 3, 3, 1>(p SEA_BIG_DIAG_ARG, st);                \
   } while (0)
   if (f16) SEA_BIG_WIDE(true); else SEA_BIG_WIDE(false);
 #undef SEA_BIG_WIDE
   return true;
 }
+
+#ifdef SEA_GEMM_BIG_DIAG
+// timing-only launches of the fp16 x 2 256 x 256 kernel (devtools/gemm_big_stamps.py): ko bits 1 no C stores, 64 non-temporal
+// C stores; step_ticks: the first round's stagger step (100 MHz ticks, at most 1250 = 100 us over 8 groups); stamps: 8 words per tile, or null
+extern "C" int sea_gemm_big_diag(const float* A, int64_t lda, const void* Wp, float* C, int64_t ldc, int M, int N, int K, int batch,
+                                 int64_t strideA, int64_t strideW_bytes, int64_t strideC, const uint32_t* amax_bits, int amax_rows,
+                                 int ko, int step_ticks, unsigned long long* stamps, void* stream) {
+  if (M <= 0 || N <= 0 || (N % 256) != 0 || K <= 0 || (K % GS_BK) != 0 || lda >= (1ll << 22) || ldc >= (1ll << 28)) return 1;
+  GemmSplitArgs p = {};
+  p.A = A; p.W = (const char*)Wp; p.C = C; p.lda = lda; p.ldc = ldc; p.strideA = strideA; p.strideW = strideW_bytes; p.strideC = strideC;
+  p.M = M; p.N = N; p.K = K; p.Npad = N;
+  p.mblocks = (M + 255) / 256; p.nblocks = N / 256; p.total = p.mblocks * p.nblocks * batch; p.per_xcd = (p.total + 7) / 8;
+  p.amax_bits = amax_bits; p.amax_rows = amax_rows; p.amax_mul = 1.f;
+  p.w_inv = (const float*)((const char*)Wp + (int64_t)(K / GS_BK) * 2 * p.Npad * GS_BK * 2);
+  int dev = 0, cus = 0;
+  (void)hipGetDevice(&dev);
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 1;
+  BigDiag dg = {0, 0, stamps};
+  if (step_ticks > 0 && step_ticks <= 1250 && p.total > cus) {
+    dg.first_round = cus;
+    dg.step_ticks = step_ticks;
+  }
+  const hipStream_t st = (hipStream_t)stream;
+  if (stamps) {
+    if (ko == 0) big_launch_one<true, 4, 2, 4, 0, 1, 0, true>(p SEA_BIG_DIAG_ARG, st);
+    else if (ko == 1) big_launch_one<true, 4, 2, 4, 0, 1, 1, true>(p SEA_BIG_DIAG_ARG, st);
+    else if (ko == 64) big_launch_one<true, 4, 2, 4, 0, 1, 64, true>(p SEA_BIG_DIAG_ARG, st);
+    else return 1;
+  } else {
+    if (ko == 0) big_launch_one<true, 4, 2, 4, 0, 1>(p SEA_BIG_DIAG_ARG, st);
+    else if (ko == 1) big_launch_one<true, 4, 2, 4, 0, 1, 1>(p SEA_BIG_DIAG_ARG, st);
+    else if (ko == 64) big_launch_one<true, 4, 2, 4, 0, 1, 64>(p SEA_BIG_DIAG_ARG, st);
+    else return 1;
+  }
+  return (int)hipGetLastError();
+}
+#endif
 
 }  // namespace sea
