@@ -326,6 +326,18 @@ int sea_upsample_bilinear_nhwc_bwd(const float* gy, float* gx, int B, int C, int
  *                               addend (B,H,W,C) / scale / bias may be NULL, act = ReLU when relu != 0.  With scale/bias = the folded
  *                               eval-mode BatchNorm this is the whole ConvModule (uperforseg.py:119-146).
  * C % 4 == 0, 16-byte aligned pointers.
+ * Matrix convention (V, U and M mean something only relative to it): the published F(2x2,3x3) / F(4x4,3x3) matrices of
+ * Lavin & Gray, "Fast Algorithms for Convolutional Neural Networks" (2015), interpolation points 0, +-1 (, +-2), infinity:
+ *   V[i*A+j] = (B^T d B)[i][j],  d = the A x A input patch whose top-left pixel is (ty*m - 1, tx*m - 1), zero outside the image
+ *   U[i*A+j] = (G g G^T)[i][j],  g = the 3 x 3 filter (rotated by 180 degrees when flip = 1)
+ *   y tile   = A^T m A,          m[i][j] = M[i*A+j], the m x m output pixels from (ty*m, tx*m); pixels beyond H, W are not written
+ *   m = 2:  B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]    G = [1 0 0; 1/2 1/2 1/2; 1/2 -1/2 1/2; 0 0 1]
+ *           A^T = [1 1 1 0; 0 1 -1 -1]
+ *   m = 4:  B^T = [4 0 -5 0 1 0; 0 -4 -4 1 1 0; 0 4 -4 -1 1 0; 0 -2 -1 2 1 0; 0 2 -1 -2 1 0; 0 4 0 -5 0 1]
+ *           G   = [1/4 0 0; -1/6 -1/6 -1/6; -1/6 1/6 -1/6; 1/24 1/12 1/6; 1/24 -1/12 1/6; 0 0 1]
+ *           A^T = [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1]
+ * oracle/sea_oracle.py (wino_input_f64 / wino_filter_f64 / wino_output_f64) restates the three transforms in float64 from
+ * these matrices; tests/test_wino_transforms_gpu.py compares every kernel variant with it.
  * vec4 (m = 4; A/B): four channels per lane instead of two; shipped: 1 in the input transforms, 0 in the output
  * transform. */
 int64_t sea_wino_tiles(int B, int H, int W, int m);

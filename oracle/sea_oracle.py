@@ -742,3 +742,102 @@ def worst_case_miou(ints: torch.Tensor, unis: torch.Tensor, orders=None, n_round
             break
         prev_best = final
     return final, sel, rounds
+
+
+# --------------------------------------------------------------------------------------------------
+# M4 : Winograd F(m x m, 3 x 3) transforms in float64 (include/sea_hip.h, M4), for the kernel tests
+# --------------------------------------------------------------------------------------------------
+# The published matrices of Lavin & Gray, "Fast Algorithms for Convolutional Neural Networks" (2015), section 4.1
+# (F(2x2,3x3)) and 4.2 (F(4x4,3x3)), written out here and not taken from the library: V, U and M are defined relative to them.
+# Not part of the reference repository, so there are no golden vectors: tests/test_wino_ref_cpu.py pins these functions to
+# conv2d and its input gradient in float64.
+_WINO_BT = {
+    2: [[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]],
+    4: [[4, 0, -5, 0, 1, 0], [0, -4, -4, 1, 1, 0], [0, 4, -4, -1, 1, 0], [0, -2, -1, 2, 1, 0], [0, 2, -1, -2, 1, 0],
+        [0, 4, 0, -5, 0, 1]],
+}
+_WINO_G = {
+    2: [[1, 0, 0], [1 / 2, 1 / 2, 1 / 2], [1 / 2, -1 / 2, 1 / 2], [0, 0, 1]],
+    4: [[1 / 4, 0, 0], [-1 / 6, -1 / 6, -1 / 6], [-1 / 6, 1 / 6, -1 / 6], [1 / 24, 1 / 12, 1 / 6], [1 / 24, -1 / 12, 1 / 6],
+        [0, 0, 1]],
+}
+_WINO_AT = {
+    2: [[1, 1, 1, 0], [0, 1, -1, -1]],
+    4: [[1, 1, 1, 1, 1, 0], [0, 1, -1, 2, -2, 0], [0, 1, 1, 4, 4, 0], [0, 1, -1, 8, -8, 1]],
+}
+
+
+def wino_matrices(m: int):
+    """(B^T (A,A), G (A,3), A^T (m,A)) of F(m x m, 3 x 3) in float64, A = m + 2; m = 2 or 4."""
+    if m not in (2, 4):
+        raise ValueError(f"F({m}x{m},3x3) is not one of the transforms of M4")
+    return tuple(torch.tensor(t[m], dtype=torch.float64) for t in (_WINO_BT, _WINO_G, _WINO_AT))
+
+
+def wino_tiles(B: int, H: int, W: int, m: int) -> int:
+    return B * (-(-H // m)) * (-(-W // m))
+
+
+def wino_input_f64(x_nhwc, m: int, gate=None, scale=None):
+    """x (B,H,W,C) -> (V, mag), both (A*A, T, C) float64: V[i*A+j][t][c] = (B^T d B)[i][j] with d the A x A patch of tile
+    t = (b, ty, tx) whose top-left pixel is (ty*m - 1, tx*m - 1), zero outside the image.  With ``gate`` (B,H,W,C) the input
+    is read as  gate > 0 ? x * scale[c] : 0  (a select: whatever x holds where the gate is closed, NaN and inf included,
+    contributes 0; a NaN gate is closed).  mag is the same computation on absolute values, |B^T| |d| |B|: the magnitude
+    that a rounding-error bound of the fp32 kernels scales with."""
+    BT, _, _ = wino_matrices(m)
+    A = m + 2
+    x = x_nhwc.double()
+    B, H, W, C = x.shape
+    if gate is not None:
+        xs = x if scale is None else x * scale.double()
+        x = torch.where(gate > 0, xs, torch.zeros_like(xs))
+    nTh, nTw = -(-H // m), -(-W // m)
+    xp = torch.zeros(B, nTh * m + 2, nTw * m + 2, C, dtype=torch.float64)
+    xp[:, 1:H + 1, 1:W + 1] = x
+    d = xp.unfold(1, A, m).unfold(2, A, m).reshape(B * nTh * nTw, C, A, A)  # (t, c, row, column)
+    V = torch.einsum("ik,tckl,jl->ijtc", BT, d, BT).reshape(A * A, -1, C)
+    mag = torch.einsum("ik,tckl,jl->ijtc", BT.abs(), d.abs(), BT.abs()).reshape(A * A, -1, C)
+    return V, mag
+
+
+def wino_filter_f64(w, m: int, flip):
+    """w (Cout,Cin,3,3) -> (U, mag) float64: U[i*A+j] = (G g G^T)[i][j], laid out (A*A, Cin, Cout) for flip = 0 and
+    (A*A, Cout, Cin), of the filters rotated by 180 degrees, for flip = 1 (the convolution that turns the output gradient
+    into the input gradient).  mag = |G| |g| |G^T|."""
+    _, G, _ = wino_matrices(m)
+    A = m + 2
+    g = w.double()
+    if flip:
+        g = g.flip(2, 3)
+    Cout, Cin = g.shape[:2]
+    U = torch.einsum("ik,ockl,jl->ijoc", G, g, G)
+    mag = torch.einsum("ik,ockl,jl->ijoc", G.abs(), g.abs(), G.abs())
+    if not flip:
+        U, mag = U.transpose(2, 3), mag.transpose(2, 3)
+    shape = (A * A, Cout, Cin) if flip else (A * A, Cin, Cout)
+    return U.reshape(shape), mag.reshape(shape)
+
+
+def wino_output_f64(M, B: int, H: int, W: int, m: int, addend=None, scale=None, bias=None, relu=False):
+    """M (A*A, T, C) -> (y, mag) (B,H,W,C) float64: the m x m pixels of tile t from (ty*m, tx*m) are A^T m A with
+    m[i][j] = M[i*A+j][t]; pixels beyond H, W are dropped;  y = act(scale[c] * (that + addend) + bias[c]), addend (B,H,W,C),
+    act = ReLU when ``relu``.  mag = |scale| * (|A^T| |m| |A| + |addend|) + |bias|  (|scale| = 1 when absent)."""
+    _, _, AT = wino_matrices(m)
+    A = m + 2
+    C = M.shape[2]
+    nTh, nTw = -(-H // m), -(-W // m)
+    mm = M.double().reshape(A, A, B, nTh, nTw, C)
+
+    def back(at, t):
+        return torch.einsum("pi,ijbyxc,qj->bypxqc", at, t, at).reshape(B, nTh * m, nTw * m, C)[:, :H, :W]
+
+    y, mag = back(AT, mm), back(AT.abs(), mm.abs())
+    if addend is not None:
+        y, mag = y + addend.double(), mag + addend.double().abs()
+    if scale is not None:
+        y, mag = y * scale.double(), mag * scale.double().abs()
+    if bias is not None:
+        y, mag = y + bias.double(), mag + bias.double().abs()
+    if relu:
+        y = torch.relu(y)
+    return y, mag

@@ -1088,6 +1088,78 @@ WINO_SPLIT_MIN_TILES = int(os.environ.get("SEA_WINO_SPLIT_MIN_TILES", "16"))
 WINO_IN_VEC4 = int(os.environ.get("SEA_WINO_IN_VEC4", "1"))
 
 
+def _wino_vector(v, n, what):
+    if v is not None and (v.dtype != torch.float32 or v.numel() != n or not v.is_contiguous()):
+        raise SeaNativeError(f"{what}: per-channel vectors must be contiguous float32 of the channel count")
+
+
+def wino_input_transform(x, m: int, gate=None, gate_scale=None, vec4: int = None, amax=None, out=None):
+    """Winograd input transform of a channels_last (B,C,H,W) tensor (or channel slice of a wider one): V (A*A, T, C), A = m + 2,
+    T = B * ceil(H/m) * ceil(W/m) (include/sea_hip.h, M4).  ``gate`` (dense channels_last, x's shape) / ``gate_scale`` (C): the
+    input is read as gate > 0 ? x * gate_scale[c] : 0.  ``out``: the V to fill, or a channel slice [.., .., c0:c0+C] of a wider
+    V (inputs of a virtual concatenation are transformed side by side).  ``amax``: an int32 tensor of T pre-zeroed words, or
+    True to allocate one: the float bits of max|V[.][t][.]| are max-accumulated into word t (calls that fill slices of one V
+    share the words), and (V, words) is returned instead of V.  ``vec4``: per-call override of bit 0 of the A/B mask
+    ``WINO_IN_VEC4`` (m = 4: four channels per lane, shipped, or two; both give the same bits)."""
+    words = amax if isinstance(amax, torch.Tensor) else None
+    _dev(x, gate, gate_scale, out, words)
+    xps = cl_pixel_stride(x)
+    if xps is None:
+        raise SeaNativeError("wino_input_transform: a channels_last float32 (B,C,H,W) tensor (or channel slice), C % 4 == 0, expected")
+    B, Cc, H, W = x.shape
+    if gate is not None and (gate.shape != x.shape or cl_pixel_stride(gate) != Cc):
+        raise SeaNativeError("wino_input_transform: gate must be a dense channels_last tensor of the input's shape")
+    _wino_vector(gate_scale, Cc, "wino_input_transform")
+    L = lib()
+    T = L.sea_wino_tiles(B, H, W, m)
+    if T <= 0:
+        raise SeaNativeError("wino_input_transform: m must be 2 or 4 and the input not empty")
+    A2 = (m + 2) ** 2
+    if out is None:
+        out = torch.empty(A2, T, Cc, dtype=torch.float32, device=x.device)
+    elif (out.dtype != torch.float32 or tuple(out.shape) != (A2, T, Cc) or out.stride(2) != 1 or out.stride(1) < Cc
+          or out.stride(0) != T * out.stride(1)):
+        raise SeaNativeError("wino_input_transform: out must be a float32 (A*A, T, C) tensor or a channel slice of a wider one")
+    vec4 = (WINO_IN_VEC4 & 1) if vec4 is None else int(bool(vec4))
+    if amax is None or amax is False:
+        _check(L.sea_wino_input_transform(_p(x), xps, _p(gate), _p(gate_scale), _p(out), out.stride(1), B, Cc, H, W, m, vec4,
+                                          _stream()), "sea_wino_input_transform")
+        return out
+    if words is None:
+        words = torch.zeros(T, dtype=torch.int32, device=x.device)
+    elif words.dtype != torch.int32 or words.numel() != T or not words.is_contiguous():
+        raise SeaNativeError("wino_input_transform: amax must be a contiguous int32 tensor of one (pre-zeroed) word per tile")
+    _check(L.sea_wino_input_transform_amax(_p(x), xps, _p(gate), _p(gate_scale), _p(out), out.stride(1), B, Cc, H, W, m, vec4,
+                                           _p(words), _stream()), "sea_wino_input_transform_amax")
+    return out, words
+
+
+def wino_output_transform(M, shape, m: int, addend=None, scale=None, bias=None, relu: bool = False, vec4: int = None,
+                          out=None):
+    """Winograd output transform of the products M (A*A, T, C) into a channels_last ``shape`` = (B,C,H,W) tensor:
+    act(scale[c] * (A^T m A + addend) + bias[c]), addend dense channels_last of that shape, act = ReLU when ``relu``
+    (include/sea_hip.h, M4).  ``out``: a dense channels_last tensor to fill.  ``vec4``: per-call override of bit 1 of the A/B
+    mask ``WINO_IN_VEC4`` (m = 4: four channels per lane, or two, shipped; both give the same bits)."""
+    _dev(M, addend, scale, bias, out)
+    B, Cc, H, W = shape
+    L = lib()
+    T = L.sea_wino_tiles(B, H, W, m)
+    if T <= 0 or Cc <= 0 or Cc % 4 or tuple(M.shape) != ((m + 2) ** 2, T, Cc):
+        raise SeaNativeError("wino_output_transform: m = 2 or 4, C % 4 == 0 and products of shape (A*A, T, C) expected")
+    if addend is not None and (tuple(addend.shape) != (B, Cc, H, W) or cl_pixel_stride(addend) != Cc):
+        raise SeaNativeError("wino_output_transform: addend must be a dense channels_last (B,C,H,W) float32 tensor")
+    _wino_vector(scale, Cc, "wino_output_transform")
+    _wino_vector(bias, Cc, "wino_output_transform")
+    if out is None:
+        out = torch.empty(B, Cc, H, W, dtype=torch.float32, device=M.device, memory_format=torch.channels_last)
+    elif tuple(out.shape) != (B, Cc, H, W) or cl_pixel_stride(out) != Cc:
+        raise SeaNativeError("wino_output_transform: out must be a dense channels_last (B,C,H,W) float32 tensor")
+    vec4 = ((WINO_IN_VEC4 >> 1) & 1) if vec4 is None else int(bool(vec4))
+    _check(L.sea_wino_output_transform(_p(_f32c(M)), _p(addend), _p(scale), _p(bias), int(relu), _p(out), B, Cc, H, W, m, vec4,
+                                       _stream()), "sea_wino_output_transform")
+    return out
+
+
 def wino_conv3x3_cl(x, U, m: int, bias=None, scale=None, relu: bool = False, gate=None, gate_scale=None,
                     addend=None, gemm_terms: int = 0):
     """3x3 / stride 1 / pad 1 convolution of a channels_last (B,Cin,H,W) tensor (or channel slice) -- or of the
@@ -1107,24 +1179,18 @@ def wino_conv3x3_cl(x, U, m: int, bias=None, scale=None, relu: bool = False, gat
     if gate is not None and (len(xs) != 1 or gate.shape != xs[0].shape or cl_pixel_stride(gate) != Cin):
         raise SeaNativeError("wino_conv3x3_cl: gate must match the (single) input's shape and layout")
     for v, n in ((bias, Cout), (scale, Cout), (gate_scale, Cin)):
-        if v is not None and (v.dtype != torch.float32 or v.numel() != n or not v.is_contiguous()):
-            raise SeaNativeError("wino_conv3x3_cl: per-channel vectors must be contiguous float32 of the channel count")
-    L = lib()
-    T = L.sea_wino_tiles(B, H, W, m)
+        _wino_vector(v, n, "wino_conv3x3_cl")
+    if addend is not None and (tuple(addend.shape) != (B, Cout, H, W) or cl_pixel_stride(addend) != Cout):
+        raise SeaNativeError("wino_conv3x3_cl: addend must be a dense channels_last (B,Cout,H,W) float32 tensor")
+    T = lib().sea_wino_tiles(B, H, W, m)
     V = torch.empty(A2, T, Cin, dtype=torch.float32, device=xs[0].device)
     off = 0
     use_split = gemm_terms in (1, 2, 3, 22) and Cin % 32 == 0 and T // B >= WINO_SPLIT_MIN_TILES
     # fp16 x 2: one scale word per tile (= per row of the Winograd-domain GEMMs), filled by the transform itself
     v_amax = (torch.zeros(T, dtype=torch.int32, device=xs[0].device)
               if (use_split and gemm_terms == 22 and AMAX_FROM_PRODUCERS) else None)
-    for t, xps in zip(xs, strides):
-        if v_amax is not None:
-            _check(L.sea_wino_input_transform_amax(_p(t), xps, _p(gate), _p(gate_scale), V.data_ptr() + 4 * off, Cin, B,
-                                                   t.shape[1], H, W, m, WINO_IN_VEC4 & 1, _p(v_amax), _stream()),
-                   "sea_wino_input_transform_amax")
-        else:
-            _check(L.sea_wino_input_transform(_p(t), xps, _p(gate), _p(gate_scale), V.data_ptr() + 4 * off, Cin, B, t.shape[1],
-                                              H, W, m, WINO_IN_VEC4 & 1, _stream()), "sea_wino_input_transform")
+    for t in xs:
+        wino_input_transform(t, m, gate, gate_scale, amax=v_amax, out=V[:, :, off:off + t.shape[1]])
         off += t.shape[1]
     if use_split:
         # M8: the (A*A) Winograd-domain products on the bf16 matrix cores (operands split into bf16 terms, fp32 accumulate)
@@ -1143,12 +1209,7 @@ def wino_conv3x3_cl(x, U, m: int, bias=None, scale=None, relu: bool = False, gat
         with torch.autocast("cuda", enabled=False):
             Mx = _f32c(torch.bmm(V, U))  # (A*A) independent fp32 GEMMs: hipBLASLt strided-batched
     del V
-    y = torch.empty(B, Cout, H, W, dtype=torch.float32, device=xs[0].device, memory_format=torch.channels_last)
-    if addend is not None and (tuple(addend.shape) != (B, Cout, H, W) or cl_pixel_stride(addend) != Cout):
-        raise SeaNativeError("wino_conv3x3_cl: addend must be a dense channels_last (B,Cout,H,W) float32 tensor")
-    _check(L.sea_wino_output_transform(_p(Mx), _p(addend), _p(scale), _p(bias), int(relu), _p(y), B, Cout, H, W, m,
-                                       (WINO_IN_VEC4 >> 1) & 1, _stream()), "sea_wino_output_transform")
-    return y
+    return wino_output_transform(Mx, (B, Cout, H, W), m, addend, scale, bias, relu)
 
 
 # A/B switches of the depthwise launcher (env SEA_DWCONV_AB, a bit mask: sea_dwconv7x7_nhwc in include/sea_hip.h; 0 = shipped)
