@@ -1,0 +1,106 @@
+#!/usr/bin/env python3
+"""T2u (csrc/train_loss_up.hip) against the two unfused device paths: event-timed forward + backward from LOW-resolution
+logits at the training size.
+
+    python devtools/train_loss_up_bench.py [--pairs 7] [--B 8] [--size 512]
+
+B x C x (size / f) x (size / f) fp32 logits (C = 21 and 151, f = 4 and 16, ``z_y += 6`` on 70 % of the low-resolution
+pixels of a blocky label map, 5 % of the labels ignored), CrossEntropy and OhemCrossEntropy (threshold regime).  Three
+variants alternate inside one process:
+
+    a  ``_up`` (M2) + F.cross_entropy / the plain module      (the UperNet branch without the switch)
+    b  ``_up`` (M2) + T2                                      (``native=True`` on the up-sampled logits)
+    c  T2u                                                    (``native=True``, ``.upsampled()``)
+
+Per row: the minimum and the second-smallest time over the pairs (warm: the same tensors every repeat, two warm-up steps per
+variant first), the peak allocation of each variant above what the inputs hold (torch.cuda.max_memory_allocated), and T2u's
+achieved bytes per second on its byte model: both kernels read the low-resolution logits and the int64 labels, the forward
+writes the loss plane, the backward reads it (OHEM) and writes the low-resolution gradient; the OHEM select's passes over the
+4-byte plane are not counted.  The time is NOT memory-bound at these sizes (the byte model is 1/10 or less of the unfused
+paths'): the figure is there to compare with K2u's, not as a share of a roofline.  One JSON line per row."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "robust-segmentation_amd")]
+
+import torch  # noqa: E402
+
+
+def make(C, B, S, f, dev):
+    g = torch.Generator(device=dev).manual_seed(C + f)
+    h = S // f
+    yl = torch.randint(0, C, (B, h, h), generator=g, device=dev)
+    z = torch.randn(B, C, h, h, generator=g, device=dev) * 3
+    z.scatter_add_(1, yl[:, None], ((torch.rand(B, h, h, generator=g, device=dev) < 0.7).float() * 6.0)[:, None])
+    y = yl.repeat_interleave(f, 1).repeat_interleave(f, 2).contiguous()
+    y[torch.rand(B, S, S, generator=g, device=dev) < 0.05] = -1
+    return z.requires_grad_(True), y
+
+
+def timed(fn, z):
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    z.grad = None
+    fn().backward()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3, torch.cuda.max_memory_allocated() - base
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pairs", type=int, default=7)
+    ap.add_argument("--B", type=int, default=8)
+    ap.add_argument("--size", type=int, default=512)
+    args = ap.parse_args()
+    assert args.pairs >= 5
+    assert torch.cuda.is_available(), "this benchmark needs the GPU"
+    from semseg import _native as N
+    from semseg.losses import CrossEntropy, OhemCrossEntropy
+    from semseg.models.convnext_upernet import _up
+    dev = torch.device("cuda:0")
+    for C in (21, 151):
+        for f in (4, 16):
+            for kind in ("CrossEntropy", "OhemCrossEntropy"):
+                z, y = make(C, args.B, args.size, f, dev)
+                cls = CrossEntropy if kind == "CrossEntropy" else OhemCrossEntropy
+                plain, native = cls(-1).to(dev), cls(-1, native=True).to(dev)
+                size = y.shape[-2:]
+                variants = {"a_up_stock": lambda: plain(_up(z, size), y), "b_up_t2": lambda: native(_up(z, size), y),
+                            "c_t2u": lambda: native.upsampled(z, y)}
+                with torch.no_grad():
+                    vals = {k: float(fn()) for k, fn in variants.items()}
+                for fn in variants.values():      # warm-up: code objects, allocator
+                    for _ in range(2):
+                        z.grad = None
+                        fn().backward()
+                times, peaks = {k: [] for k in variants}, {k: 0 for k in variants}
+                for _ in range(args.pairs):
+                    for name, fn in variants.items():
+                        t, peak = timed(fn, z)
+                        times[name].append(t)
+                        peaks[name] = max(peaks[name], peak)
+                n, nl = args.B * args.size * args.size, z.numel()
+                model = 2 * (nl * 4 + n * 8) + n * 4 + nl * 4 + (n * 4 if kind != "CrossEntropy" else 0)
+                h = args.size // f
+                row = dict(kernel="T2u", criterion=kind, C=C, factor=f, B=args.B, size=args.size,
+                           tile=N.train_ce_up_tile(C, h, h, args.size, args.size), model_bytes=model, loss=vals)
+                for name in variants:
+                    ts = sorted(times[name])
+                    row[f"{name}_us_min"], row[f"{name}_us_2nd"] = round(ts[0], 1), round(ts[1], 1)
+                    row[f"{name}_peak_MB"] = round(peaks[name] / 2 ** 20, 1)
+                row["c_GBs_on_model"] = round(model / (row["c_t2u_us_min"] * 1e-6) / 1e9, 1)
+                row["a_over_c"] = round(row["a_up_stock_us_min"] / row["c_t2u_us_min"], 2)
+                row["b_over_c"] = round(row["b_up_t2_us_min"] / row["c_t2u_us_min"], 2)
+                print(json.dumps(row), flush=True)
+                del z, y, variants
+
+
+if __name__ == "__main__":
+    main()

@@ -739,6 +739,38 @@ int sea_train_ce_bwd(const void* logits, int dtype, const int64_t* y, const floa
                      int B, int C, int64_t HW, const float* loss_px, const float* g, const void* words, void* dlogits,
                      void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * T2u: T2 fused with the model's final bilinear up-sampling.  Replaces, for one prediction of UperNet's training
+ * forward, F.interpolate(low, (H, W), mode="bilinear", align_corners=False) + the criterion + both backward passes:
+ * the (B, C, H, W) logits, their log-soft-max and their gradients are never materialised.
+ * low: dense NCHW fp32 (B, C, h, w), 2 <= C <= 192; y: int64 labels (B, H, W), H >= h, W >= w, any ratio up to 28 per
+ * axis (power of two or not); wgt: C class weights or NULL.  Outside these limits every entry point returns the argument
+ * error (workspace_bytes: 0) and launches nothing; the caller then up-samples and calls T2.  B*H*W < 2^31.
+ * Interpolation: ATen's upsample_bilinear2d, align_corners = 0: src = max(r*(dst+0.5)-0.5, 0), i1 = min(i0+1, n-1).
+ * Everything else is T2's: labels, `words` (the same 64 bytes, ZEROED by the caller before the forward), the loss plane
+ * loss_px (B*H*W floats at FULL resolution), the records summed in a fixed order in double, reduce_mean, thresh.
+ * Nothing is read by the host; no float atomics: bitwise reproducible.
+ * sea_train_ce_up_tile: edge TL of the low-resolution tile one workgroup owns for this shape (0: no plan).  A
+ *   workgroup owns the loss of the full-resolution pixels whose top-left source pixel lies in its tile and the gradient
+ *   of the tile; it recomputes the statistics of the one-cell halo of full-resolution pixels around it.
+ * sea_train_ce_up_workspace_bytes: bytes of `workspace` (16-byte aligned); laid out as T2's, so that
+ *   sea_train_ohem_select runs UNCHANGED on loss_px (N = B*H*W) with the same workspace and words after
+ *   sea_train_ce_up_fwd with reduce_mean = 0.
+ * sea_train_ce_up_fwd: per full-resolution pixel w[y]*(lse(z) - z_y) of the interpolated logits z, 0 where ignored, into
+ *   loss_px; then the words as sea_train_ce_fwd.
+ * sea_train_ce_up_bwd: dlow[b,c,i,j] = g[0] * coef * sum over the valid (ohem = 1: selected, loss_px != -1) pixels whose
+ *   bilinear footprint touches (i, j) of weight * w[y] * (softmax(z)_c - [c == y]); a gather with one owner per element
+ *   of dlow, summed cell by cell, row by row in double.  Every element of dlow is written.  workspace: unused by the
+ *   gather (may be NULL). */
+int sea_train_ce_up_tile(int C, int h, int w, int H, int W);
+size_t sea_train_ce_up_workspace_bytes(int B, int C, int h, int w, int H, int W);
+int sea_train_ce_up_fwd(const float* low, const int64_t* y, const float* wgt, int64_t ignore_label, float thresh,
+                        int reduce_mean, int B, int C, int h, int w, int H, int W, float* loss_px, void* workspace,
+                        size_t workspace_bytes, void* words, void* stream);
+int sea_train_ce_up_bwd(const float* low, const int64_t* y, const float* wgt, int64_t ignore_label, int ohem, int B, int C,
+                        int h, int w, int H, int W, const float* loss_px, const float* g, const void* words, float* dlow,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

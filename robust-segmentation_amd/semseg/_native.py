@@ -128,6 +128,10 @@ _SIGS = {
     "sea_train_ce_fwd": (_i, [_vp, _i, _vp, _vp, _i64, _f, _i, _i, _i, _i64, _vp, _vp, _sz, _vp, _vp]),
     "sea_train_ohem_select": (_i, [_vp, _i64, _vp, _sz, _vp, _vp]),
     "sea_train_ce_bwd": (_i, [_vp, _i, _vp, _vp, _i64, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "sea_train_ce_up_tile": (_i, [_i, _i, _i, _i, _i]),
+    "sea_train_ce_up_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "sea_train_ce_up_fwd": (_i, [_vp, _vp, _vp, _i64, _f, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _vp]),
+    "sea_train_ce_up_bwd": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -428,6 +432,76 @@ def train_ce_backward(logits, y, weight, ignore_label: int, ohem: bool, loss_px,
                                   1 if ohem else 0, B, Cc, HW, _p(_f32c(loss_px)), _p(g), _p(words), _p(dlogits),
                                   _stream()), "sea_train_ce_bwd")
     return dlogits
+
+
+# ------------------------------------------------------------------------------------------------ T2u
+TRAIN_UP_CLASSES = (2, 192)    # csrc/train_loss_up.hip: kUpMinClasses, kUpMaxClasses
+
+
+def _train_up_args(low, size, y, weight):
+    _dev(low, y, weight)
+    if low.dim() != 4 or not low.is_contiguous():
+        raise SeaNativeError("the fused criterion takes dense NCHW low-resolution logits (B,C,h,w)")
+    if low.dtype != torch.float32:
+        raise SeaNativeError(f"the fused criterion takes float32 logits, got {low.dtype}: cast the small tensor up first")
+    B, Cc, h, w = low.shape
+    H, W = (int(v) for v in size)
+    if H < h or W < w:
+        raise SeaNativeError(f"the fused criterion up-samples: target {(H, W)} is smaller than the logits {(h, w)}")
+    if y.dtype != torch.int64 or y.shape != (B, H, W) or not y.is_contiguous():
+        raise SeaNativeError("labels must be a contiguous int64 (B,H,W) tensor at the target size")
+    if weight is not None:
+        weight = _f32c(weight)
+        if weight.numel() != Cc:
+            raise SeaNativeError("class weights must have C entries")
+    return B, Cc, h, w, H, W, weight
+
+
+def train_ce_up_supported(low, size) -> bool:
+    """Whether T2u has a kernel for this shape (class count 2..192, a tiling for the ratio); the caller takes
+    ``F.interpolate`` + T2 otherwise."""
+    B, Cc, h, w = low.shape
+    return lib().sea_train_ce_up_workspace_bytes(B, Cc, h, w, int(size[0]), int(size[1])) != 0
+
+
+def train_ce_up_tile(C: int, h: int, w: int, H: int, W: int) -> int:
+    """Edge of the low-resolution tile one workgroup owns for this shape (0: no T2u kernel)."""
+    return int(lib().sea_train_ce_up_tile(C, h, w, H, W))
+
+
+def train_ce_up_forward(low, size, y, weight, ignore_label: int, thresh: float = 0.0, ohem: bool = False):
+    """T2u forward (+ the OHEM select, T2's, on the full-resolution loss plane) on LOW-resolution logits (B,C,h,w);
+    ``size`` = (H, W) of the labels.  Returns (loss, loss_px, words) as ``train_ce_forward``.  Nothing is read by the host."""
+    B, Cc, h, w, H, W, weight = _train_up_args(low, size, y, weight)
+    dev = low.device
+    L = lib()
+    nb = L.sea_train_ce_up_workspace_bytes(B, Cc, h, w, H, W)
+    if nb == 0:
+        raise SeaNativeError(f"no T2u kernel for C = {Cc}, {(h, w)} -> {(H, W)}")
+    workspace = torch.empty(nb, dtype=torch.uint8, device=dev)
+    words = torch.zeros(8, dtype=torch.float64, device=dev)
+    loss_px = torch.empty(B, H * W, dtype=torch.float32, device=dev)
+    _check(L.sea_train_ce_up_fwd(_p(low), _p(y), _p(weight), int(ignore_label), float(thresh), 0 if ohem else 1, B, Cc,
+                                 h, w, H, W, _p(loss_px), _p(workspace), nb, _p(words), _stream()),
+           "sea_train_ce_up_fwd")
+    if ohem:
+        _check(L.sea_train_ohem_select(_p(loss_px), B * H * W, _p(workspace), nb, _p(words), _stream()),
+               "sea_train_ohem_select")
+    return words.view(torch.float32)[TRAIN_WORDS_F32["loss"]].clone(), loss_px, words
+
+
+def train_ce_up_backward(low, size, y, weight, ignore_label: int, ohem: bool, loss_px, words, g):
+    """T2u backward: d loss / d low (fp32, every element written).  ``g``: the upstream gradient, a 0-dim device tensor."""
+    B, Cc, h, w, H, W, weight = _train_up_args(low, size, y, weight)
+    _dev(loss_px, words, g)
+    if g.numel() != 1:
+        raise SeaNativeError("the upstream gradient of the criterion is a scalar")
+    g = g.reshape(1).to(torch.float32)
+    dlow = torch.empty_like(low)
+    _check(lib().sea_train_ce_up_bwd(_p(low), _p(y), _p(weight), int(ignore_label), 1 if ohem else 0, B, Cc, h, w, H, W,
+                                     _p(_f32c(loss_px)), _p(g), _p(words), _p(dlow), None, 0, _stream()),
+           "sea_train_ce_up_bwd")
+    return dlow
 
 
 # ------------------------------------------------------------------------------------------------ K3

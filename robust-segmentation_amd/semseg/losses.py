@@ -6,7 +6,13 @@ fused forward, hard-pixel selection and backward, no host read, no log-softmax k
 on the HIP device raises ``SeaNativeError`` (no CPU fallback), and so do logits that are neither dense NCHW nor
 channels_last; channels_last logits, for which T2 has no kernel, go through the PyTorch criterion (with its host
 synchronisations for OHEM).  The native loss is an fp32 scalar whatever the logits' dtype.  ``Dice`` stays PyTorch: it takes probabilities, and no configuration of the reference
-uses it."""
+uses it.
+
+Both criteria also have ``upsampled(preds_low, labels)``: the value and gradient of ``self(F.interpolate(p, labels.shape[-2:],
+mode="bilinear", align_corners=False), labels)`` for the low-resolution output ``p`` of a model head (a tensor, or a tuple with
+``aux_weights``).  With ``native=False`` it is exactly that composition; with ``native=True`` it runs T2u
+(csrc/train_loss_up.hip), which interpolates inside the criterion's kernels: the full-resolution logits and their gradient are
+never created.  A class count T2u has no kernel for (outside 2..192) takes the composition with T2."""
 from __future__ import annotations
 
 import torch
@@ -51,6 +57,30 @@ def _native_forward(module, preds, labels, thresh, ohem):
     return loss
 
 
+class _NativeCriterionUp(torch.autograd.Function):
+    """T2u: as ``_NativeCriterion`` on low-resolution logits; the labels' size is the up-sampling target."""
+
+    @staticmethod
+    def forward(ctx, low, labels, weight, ignore_label, thresh, ohem):
+        from . import _native as N
+        loss, loss_px, words = N.train_ce_up_forward(low, labels.shape[-2:], labels, weight, ignore_label, thresh, ohem)
+        ctx.save_for_backward(low, labels, loss_px, words)
+        ctx.weight, ctx.ignore_label, ctx.ohem = weight, ignore_label, ohem
+        ctx.mark_non_differentiable(words)
+        return loss, words
+
+    @staticmethod
+    def backward(ctx, g, _g_words):
+        from . import _native as N
+        low, labels, loss_px, words = ctx.saved_tensors
+        return (N.train_ce_up_backward(low, labels.shape[-2:], labels, ctx.weight, ctx.ignore_label, ctx.ohem, loss_px,
+                                       words, g), None, None, None, None, None)
+
+
+def _upsample(p, labels):
+    return F.interpolate(p, size=labels.shape[-2:], mode="bilinear", align_corners=False)
+
+
 class _AuxWeighted(nn.Module):
     aux_weights: list
 
@@ -63,7 +93,35 @@ class _AuxWeighted(nn.Module):
         return self._forward(preds, labels)
 
 
-class CrossEntropy(_AuxWeighted):
+class _Upsampled(_AuxWeighted):
+    """``upsampled`` of the two cross-entropy criteria (module docstring)."""
+    _ohem = False
+
+    def _thresh(self) -> float:
+        return 0.0
+
+    def upsampled(self, preds_low, labels: Tensor) -> Tensor:
+        if isinstance(preds_low, tuple):
+            return sum(w * self._upsampled(p, labels) for p, w in zip(preds_low, self.aux_weights))
+        return self._upsampled(preds_low, labels)
+
+    def _upsampled(self, low, labels):
+        if self.native:
+            from . import _native as N
+            if not (low.is_cuda and labels.is_cuda):
+                raise N.SeaNativeError("native=True criteria work on HIP device tensors only (no CPU fallback)")
+            if low.dim() == 4 and N.train_ce_up_supported(low, labels.shape[-2:]):
+                w = self.criterion.weight
+                loss, self.last_words = _NativeCriterionUp.apply(
+                    low.float().contiguous(), labels, None if w is None else w.detach().float(),
+                    self.criterion.ignore_index, self._thresh(), self._ohem)
+                return loss
+            from .models.convnext_upernet import _up   # no T2u kernel for this shape: M2 up-sampling + T2
+            return self._forward(_up(low, labels.shape[-2:]), labels)
+        return self._forward(_upsample(low, labels), labels)
+
+
+class CrossEntropy(_Upsampled):
     def __init__(self, ignore_label: int = 255, weight: Tensor = None, aux_weights=(1, 0.4, 0.4),
                  native: bool = False) -> None:
         super().__init__()
@@ -80,7 +138,12 @@ class CrossEntropy(_AuxWeighted):
         return self.criterion(preds, labels)
 
 
-class OhemCrossEntropy(_AuxWeighted):
+class OhemCrossEntropy(_Upsampled):
+    _ohem = True
+
+    def _thresh(self) -> float:
+        return float(self.thresh)
+
     def __init__(self, ignore_label: int = 255, weight: Tensor = None, thresh: float = 0.7, aux_weights=(1, 1),
                  native: bool = False) -> None:
         super().__init__()

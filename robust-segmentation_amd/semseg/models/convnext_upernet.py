@@ -84,6 +84,10 @@ class _LayerNormHip(torch.autograd.Function):
 # weight / bias takes M5's forward and T3a's backward (dx, dw, db), and Block.forward gets a branch for any drop rate
 # (depthwise M1 / M1w, T3a, the fused layer-scale / stochastic-depth / residual tail T3b).  fp32 only.
 TRAIN_NATIVE_BLOCKS = os.environ.get("SEA_TRAIN_BLOCKS", "0") not in ("", "0")
+# T2u (csrc/train_loss_up.hip): the training forward hands the heads' 1/4-resolution logits to the criterion, which
+# interpolates inside its kernels; the full-resolution logits are never created and forward returns (loss, None).
+# Read once at import; tools/train_rob_seg.py --fused-criterion sets it for a run.
+TRAIN_FUSED_CRITERION = os.environ.get("SEA_TRAIN_FUSED_LOSS", "0") not in ("", "0")
 
 
 class _LayerNormHipTrain(torch.autograd.Function):
@@ -1547,6 +1551,17 @@ def _head_init(m):
             m.bias.data.zero_()
 
 
+_FUSED_CRITERION = []
+
+
+def _fused_criterion():
+    """the criterion of the fused training branch: F.cross_entropy(ignore_index=-1) on the device through T2u"""
+    if not _FUSED_CRITERION:
+        from ..losses import CrossEntropy
+        _FUSED_CRITERION.append(CrossEntropy(ignore_label=-1, native=True))
+    return _FUSED_CRITERION[0]
+
+
 class UperNetForSemanticSegmentation(nn.Module):
     """``UperNetForSemanticSegmentation("ConvNeXt-T_CVST", n_cls, pretrained)`` (uperforseg.py:382-404)."""
 
@@ -1589,6 +1604,12 @@ class UperNetForSemanticSegmentation(nn.Module):
             with torch.autocast("cuda", enabled=False), _gemm_terms(GEMM_TERMS_AUTOCAST_MODEL):
                 return _up(self.decode_head(self.backbone(input)).contiguous(), input.shape[2:])
         feats = self.backbone(input)
+        if (TRAIN_FUSED_CRITERION and lbl is not None and self.training and input.is_cuda
+                and input.dtype == torch.float32):
+            crit = _fused_criterion()
+            main = self._head_logits(feats).float().contiguous()
+            aux = self.auxiliary_head(feats).float().contiguous()
+            return crit.upsampled(main, lbl) + 0.4 * crit.upsampled(aux, lbl), None
         logits = _up(self._head_logits(feats).contiguous(), input.shape[2:])  # NCHW logits for K2
         loss = None
         if lbl is not None:

@@ -23,6 +23,8 @@ parameter groups (layer0-4, then ppm, cls, aux) and the poly rule set after ever
 warm-up (SCHEDULER is ignored).  Its crops satisfy (H - 1) % 8 == 0.
 ``--native-blocks`` runs the fp32 outer step's ConvNeXt trunk in NHWC on libsea_hip for this run (T3: LayerNorm with
 parameter gradients, fused stochastic-depth tail; ``semseg.models.convnext_upernet.TRAIN_NATIVE_BLOCKS``).
+``--fused-criterion`` fuses the UperNet branch's final up-sampling into its two cross-entropies for this run (T2u;
+``semseg.models.convnext_upernet.TRAIN_FUSED_CRITERION``).
 """
 from __future__ import annotations
 
@@ -151,9 +153,15 @@ def _main(argv=None):
     ap.add_argument("--native-blocks", action="store_true",
                     help="ConvNeXt trunk: train-mode blocks and trainable LayerNorms in NHWC on libsea_hip (T3, fp32; "
                          "csrc/ln_kernels.hip, csrc/block_tail.hip) for this run")
+    ap.add_argument("--fused-criterion", action="store_true",
+                    help="UperNet branch: the outer step's cross-entropies take the heads' 1/4-resolution logits and "
+                         "interpolate inside the criterion (T2u, csrc/train_loss_up.hip) for this run; no "
+                         "full-resolution logits are created")
     args = ap.parse_args(argv)
     if args.native_blocks:
         _convnext.TRAIN_NATIVE_BLOCKS = True
+    if args.fused_criterion:
+        _convnext.TRAIN_FUSED_CRITERION = True
     with open(args.cfg) as f:
         cfg = yaml.load(f, Loader=yaml.SafeLoader)
     train_cfg, model_cfg, data_cfg = cfg["TRAIN"], cfg["MODEL"], cfg["DATASET"]
@@ -284,6 +292,7 @@ def _main(argv=None):
                "inner_image_iterations_per_s": world * bs * args.steps * n_inner / dt,
                "ms_per_outer_step": dt * 1e3 / args.steps, "last_loss": float(loss)}
         out["native_blocks"] = bool(_convnext.TRAIN_NATIVE_BLOCKS)
+        out["fused_criterion"] = bool(_convnext.TRAIN_FUSED_CRITERION)
         print(json.dumps(out))
         if args.json:
             json.dump(out, open(args.json, "w"))
@@ -298,15 +307,17 @@ def _main(argv=None):
 
 
 def main(argv=None):
-    """`_main` with the process-global switches it sets (MIOpen find mode, ``--native-blocks``) restored on exit: a caller
+    """`_main` with the process-global switches it sets (MIOpen find mode, ``--native-blocks``, ``--fused-criterion``) restored on exit: a caller
     that runs this in-process (tests do) must not inherit `cudnn.benchmark = True` or the T3 switch.  Returns rank 0's
     result record (the JSON line it prints)."""
     prev, prev_blocks = torch.backends.cudnn.benchmark, _convnext.TRAIN_NATIVE_BLOCKS
+    prev_fused = _convnext.TRAIN_FUSED_CRITERION
     try:
         return _main(argv)
     finally:
         torch.backends.cudnn.benchmark = prev
         _convnext.TRAIN_NATIVE_BLOCKS = prev_blocks
+        _convnext.TRAIN_FUSED_CRITERION = prev_fused
 
 
 if __name__ == "__main__":
