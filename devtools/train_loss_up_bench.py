@@ -5,12 +5,14 @@ logits at the training size.
     python devtools/train_loss_up_bench.py [--pairs 7] [--B 8] [--size 512]
 
 B x C x (size / f) x (size / f) fp32 logits (C = 21 and 151, f = 4 and 16, ``z_y += 6`` on 70 % of the low-resolution
-pixels of a blocky label map, 5 % of the labels ignored), CrossEntropy and OhemCrossEntropy (threshold regime).  Three
+pixels of a blocky label map, 5 % of the labels ignored), CrossEntropy and OhemCrossEntropy (threshold regime).  The
 variants alternate inside one process:
 
     a  ``_up`` (M2) + F.cross_entropy / the plain module      (the UperNet branch without the switch)
     b  ``_up`` (M2) + T2                                      (``native=True`` on the up-sampled logits)
     c  T2u                                                    (``native=True``, ``.upsampled()``)
+    d  T2u, single-pass x4 / x16 kernel                       (``native=True, up_kernel="pow2"``, ``.upsampled()``;
+                                                               CrossEntropy rows only: OHEM keeps the gather kernels)
 
 Per row: the minimum and the second-smallest time over the pairs (warm: the same tensors every repeat, two warm-up steps per
 variant first), the peak allocation of each variant above what the inputs hold (torch.cuda.max_memory_allocated), and T2u's
@@ -74,6 +76,10 @@ def main():
                 size = y.shape[-2:]
                 variants = {"a_up_stock": lambda: plain(_up(z, size), y), "b_up_t2": lambda: native(_up(z, size), y),
                             "c_t2u": lambda: native.upsampled(z, y)}
+                if kind == "CrossEntropy":
+                    pow2 = cls(-1, native=True, up_kernel="pow2").to(dev)
+                    assert N.train_ce_up_pow2_supported(z, size)
+                    variants["d_t2u_pow2"] = lambda: pow2.upsampled(z, y)
                 with torch.no_grad():
                     vals = {k: float(fn()) for k, fn in variants.items()}
                 for fn in variants.values():      # warm-up: code objects, allocator
@@ -98,6 +104,9 @@ def main():
                 row["c_GBs_on_model"] = round(model / (row["c_t2u_us_min"] * 1e-6) / 1e9, 1)
                 row["a_over_c"] = round(row["a_up_stock_us_min"] / row["c_t2u_us_min"], 2)
                 row["b_over_c"] = round(row["b_up_t2_us_min"] / row["c_t2u_us_min"], 2)
+                if "d_t2u_pow2" in variants:
+                    row["b_over_d"] = round(row["b_up_t2_us_min"] / row["d_t2u_pow2_us_min"], 2)
+                    row["c_over_d"] = round(row["c_t2u_us_min"] / row["d_t2u_pow2_us_min"], 2)
                 print(json.dumps(row), flush=True)
                 del z, y, variants
 

@@ -771,6 +771,34 @@ int sea_train_ce_up_bwd(const float* low, const int64_t* y, const float* wgt, in
                         int h, int w, int H, int W, const float* loss_px, const float* g, const void* words, float* dlow,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * T2u for power-of-two ratios (csrc/train_loss_up_pow2.hip): nn.CrossEntropyLoss(weight, ignore_index, reduction="mean")
+ * on F.interpolate(low, (H, W), mode="bilinear", align_corners=False), loss AND un-normalised gradient in ONE pass.
+ * Replaces, per prediction, uperforseg.py:416-434 (main head x4, auxiliary head x16) and segmenter.py:228 +
+ * train_rob_seg.py:346-347 (Segmenter's masks x16, then the criterion), with their backward passes.
+ * Applies when H = r*h and W = r*w with r = 4 or r = 16 on both axes, low dense NCHW fp32 (B, C, h, w), 2 <= C <= 192,
+ * h, w >= 1; y: int64 labels (B, H, W); wgt: C class weights or NULL; B*H*W < 2^31.  OHEM has no such kernel (its
+ * selection needs every loss before any gradient): it keeps sea_train_ce_up_fwd / _bwd.
+ * With mean reduction d loss / d low = g * (1 / sum w[y]) * raw, raw[b,c,i,j] = sum over the valid pixels whose bilinear
+ * footprint touches (i, j) of weight * w[y] * (softmax(z)_c - [c == y]): the forward writes raw (B*C*h*w DOUBLES, every
+ * element: the gradient is rounded to float once, by the scale pass), the backward is one scale pass.  No full-resolution plane of any kind is written.  Labels, `words` (the same
+ * 64 bytes, ZEROED by the caller) and the edge cases are T2's: a label outside [0, C) other than ignore_label is ignored
+ * and sets words.err; every label ignored gives loss = NaN, coef = inf and raw = 0.  Nothing is read by the host; no float
+ * atomics; raw[b] depends on image b alone, bit for bit.  A refused call returns the argument error and writes nothing.
+ * sea_train_ce_up_pow2_supported (host only): 1 if the shape is one of the above, else 0.
+ * sea_train_ce_up_pow2_workspace_bytes: bytes of `workspace` (16-byte aligned: per-wave records and partial gradient
+ *   vectors, 2*(h+1)*(w + segments)*C doubles per image); 0 if unsupported.
+ * sea_train_ce_up_pow2_fwd: raw and the words as sea_train_ce_fwd with reduce_mean = 1 writes them.
+ * sea_train_ce_up_pow2_scale: dlow[i] = (g[0] / words.sum_w) * raw[i] for i < n, the product in double and rounded once,
+ *   and exactly 0 where raw[i] is 0 (so that a batch with every label ignored gets zeros, not 0 * inf); g: one float in
+ *   device memory. */
+int sea_train_ce_up_pow2_supported(int C, int h, int w, int H, int W);
+size_t sea_train_ce_up_pow2_workspace_bytes(int B, int C, int h, int w, int H, int W);
+int sea_train_ce_up_pow2_fwd(const float* low, const int64_t* y, const float* wgt, int64_t ignore_label, int B, int C,
+                             int h, int w, int H, int W, double* raw, void* workspace, size_t workspace_bytes, void* words,
+                             void* stream);
+int sea_train_ce_up_pow2_scale(const double* raw, const float* g, const void* words, float* dlow, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,7 @@ SOURCES = [
     ("bn_train.hip", []),
     ("train_loss.hip", []),
     ("train_loss_up.hip", []),
+    ("train_loss_up_pow2.hip", []),
     ("greedy_host.cpp", ["-ffp-contract=off"]),
     ("api_misc.cpp", []),
 ]

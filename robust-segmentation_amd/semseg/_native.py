@@ -132,6 +132,10 @@ _SIGS = {
     "sea_train_ce_up_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "sea_train_ce_up_fwd": (_i, [_vp, _vp, _vp, _i64, _f, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _vp]),
     "sea_train_ce_up_bwd": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sea_train_ce_up_pow2_supported": (_i, [_i, _i, _i, _i, _i]),
+    "sea_train_ce_up_pow2_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "sea_train_ce_up_pow2_fwd": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _vp]),
+    "sea_train_ce_up_pow2_scale": (_i, [_vp, _vp, _vp, _vp, _i64, _vp]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -501,6 +505,49 @@ def train_ce_up_backward(low, size, y, weight, ignore_label: int, ohem: bool, lo
     _check(lib().sea_train_ce_up_bwd(_p(low), _p(y), _p(weight), int(ignore_label), 1 if ohem else 0, B, Cc, h, w, H, W,
                                      _p(_f32c(loss_px)), _p(g), _p(words), _p(dlow), None, 0, _stream()),
            "sea_train_ce_up_bwd")
+    return dlow
+
+
+# ------------------------------------------------------------------------------------------------ T2u, power-of-two ratios
+def train_ce_up_pow2_supported(low, size) -> bool:
+    """Whether the single-pass kernel (csrc/train_loss_up_pow2.hip) has this shape: (B,C,h,w) with 2 <= C <= 192 and
+    ``size`` exactly 4x or 16x the map on both axes.  Shapes only, as ``train_ce_up_supported``: the caller passes
+    ``.float()`` of the small tensor to the forward."""
+    if low.dim() != 4:
+        return False
+    _, Cc, h, w = low.shape
+    return bool(lib().sea_train_ce_up_pow2_supported(Cc, h, w, int(size[0]), int(size[1])))
+
+
+def train_ce_up_pow2_forward(low, size, y, weight, ignore_label: int):
+    """Mean-reduced (weighted) cross-entropy of the x4 / x16 up-sampled logits and its un-normalised gradient in one pass.
+    Returns (loss, raw, words): the 0-dim fp32 loss, ``raw`` (B,C,h,w), float64, with d loss / d low = raw / sum w[y], and the device
+    words as ``train_ce_forward``.  Nothing is read by the host."""
+    B, Cc, h, w, H, W, weight = _train_up_args(low, size, y, weight)
+    L = lib()
+    nb = L.sea_train_ce_up_pow2_workspace_bytes(B, Cc, h, w, H, W)
+    if nb == 0:
+        raise SeaNativeError(f"no single-pass kernel for C = {Cc}, {(h, w)} -> {(H, W)} (x4 / x16 only)")
+    dev = low.device
+    workspace = torch.empty(nb, dtype=torch.uint8, device=dev)
+    words = torch.zeros(8, dtype=torch.float64, device=dev)
+    raw = torch.empty(low.shape, dtype=torch.float64, device=dev)
+    _check(L.sea_train_ce_up_pow2_fwd(_p(low), _p(y), _p(weight), int(ignore_label), B, Cc, h, w, H, W, _p(raw),
+                                      _p(workspace), nb, _p(words), _stream()), "sea_train_ce_up_pow2_fwd")
+    return words.view(torch.float32)[TRAIN_WORDS_F32["loss"]].clone(), raw, words
+
+
+def train_ce_up_pow2_backward(raw, words, g):
+    """d loss / d low = (g / sum w[y]) * raw, multiplied in double (fp32, every element written).  ``g``: a 0-dim device tensor."""
+    _dev(raw, words, g)
+    if g.numel() != 1:
+        raise SeaNativeError("the upstream gradient of the criterion is a scalar")
+    g = g.reshape(1).to(torch.float32)
+    if raw.dtype != torch.float64 or not raw.is_contiguous():
+        raise SeaNativeError("raw is the contiguous float64 tensor the forward returned")
+    dlow = torch.empty(raw.shape, dtype=torch.float32, device=raw.device)
+    _check(lib().sea_train_ce_up_pow2_scale(_p(raw), _p(g), _p(words), _p(dlow), raw.numel(), _stream()),
+           "sea_train_ce_up_pow2_scale")
     return dlow
 
 

@@ -12,7 +12,12 @@ Both criteria also have ``upsampled(preds_low, labels)``: the value and gradient
 mode="bilinear", align_corners=False), labels)`` for the low-resolution output ``p`` of a model head (a tensor, or a tuple with
 ``aux_weights``).  With ``native=False`` it is exactly that composition; with ``native=True`` it runs T2u
 (csrc/train_loss_up.hip), which interpolates inside the criterion's kernels: the full-resolution logits and their gradient are
-never created.  A class count T2u has no kernel for (outside 2..192) takes the composition with T2."""
+never created.  A class count T2u has no kernel for (outside 2..192) takes the composition with T2.
+
+``up_kernel`` chooses T2u's kernel for ``upsampled``: ``"gather"`` (the default: csrc/train_loss_up.hip, any ratio, two
+launches) or ``"pow2"`` (csrc/train_loss_up_pow2.hip: forward and gradient in one pass for ``CrossEntropy`` on a prediction
+that is exactly 1/4 or 1/16 of the labels on both axes; any other prediction goes where ``"gather"`` sends it).
+``OhemCrossEntropy`` accepts the argument and keeps the gather kernels: its selection needs every loss before any gradient."""
 from __future__ import annotations
 
 import torch
@@ -77,6 +82,33 @@ class _NativeCriterionUp(torch.autograd.Function):
                                        words, g), None, None, None, None, None)
 
 
+class _NativeCriterionUpPow2(torch.autograd.Function):
+    """T2u for x4 / x16, mean-reduced cross-entropy: the forward leaves the un-normalised gradient, the backward scales it."""
+
+    @staticmethod
+    def forward(ctx, low, labels, weight, ignore_label):
+        from . import _native as N
+        loss, raw, words = N.train_ce_up_pow2_forward(low, labels.shape[-2:], labels, weight, ignore_label)
+        ctx.save_for_backward(raw, words)
+        ctx.mark_non_differentiable(words)
+        return loss, words
+
+    @staticmethod
+    def backward(ctx, g, _g_words):
+        from . import _native as N
+        raw, words = ctx.saved_tensors
+        return N.train_ce_up_pow2_backward(raw, words, g), None, None, None
+
+
+UP_KERNELS = ("gather", "pow2")
+
+
+def _check_up_kernel(up_kernel):
+    if up_kernel not in UP_KERNELS:
+        raise ValueError(f"up_kernel must be one of {UP_KERNELS}, got {up_kernel!r}")
+    return up_kernel
+
+
 def _upsample(p, labels):
     return F.interpolate(p, size=labels.shape[-2:], mode="bilinear", align_corners=False)
 
@@ -110,8 +142,14 @@ class _Upsampled(_AuxWeighted):
             from . import _native as N
             if not (low.is_cuda and labels.is_cuda):
                 raise N.SeaNativeError("native=True criteria work on HIP device tensors only (no CPU fallback)")
+            w = self.criterion.weight
+            if (self.up_kernel == "pow2" and not self._ohem
+                    and N.train_ce_up_pow2_supported(low, labels.shape[-2:])):
+                loss, self.last_words = _NativeCriterionUpPow2.apply(
+                    low.float().contiguous(), labels, None if w is None else w.detach().float(),
+                    self.criterion.ignore_index)
+                return loss
             if low.dim() == 4 and N.train_ce_up_supported(low, labels.shape[-2:]):
-                w = self.criterion.weight
                 loss, self.last_words = _NativeCriterionUp.apply(
                     low.float().contiguous(), labels, None if w is None else w.detach().float(),
                     self.criterion.ignore_index, self._thresh(), self._ohem)
@@ -123,10 +161,11 @@ class _Upsampled(_AuxWeighted):
 
 class CrossEntropy(_Upsampled):
     def __init__(self, ignore_label: int = 255, weight: Tensor = None, aux_weights=(1, 0.4, 0.4),
-                 native: bool = False) -> None:
+                 native: bool = False, up_kernel: str = "gather") -> None:
         super().__init__()
         self.aux_weights = list(aux_weights)
         self.native = native
+        self.up_kernel = _check_up_kernel(up_kernel)
         self.last_words = None      # native: the device words of the last prediction (debugging / tests)
         self.criterion = nn.CrossEntropyLoss(weight=weight, ignore_index=ignore_label)
 
@@ -145,11 +184,12 @@ class OhemCrossEntropy(_Upsampled):
         return float(self.thresh)
 
     def __init__(self, ignore_label: int = 255, weight: Tensor = None, thresh: float = 0.7, aux_weights=(1, 1),
-                 native: bool = False) -> None:
+                 native: bool = False, up_kernel: str = "gather") -> None:
         super().__init__()
         self.ignore_label = ignore_label
         self.aux_weights = list(aux_weights)
         self.native = native
+        self.up_kernel = _check_up_kernel(up_kernel)   # accepted, not used: OHEM keeps the gather kernels
         self.last_words = None
         self.thresh = -torch.log(torch.tensor(thresh, dtype=torch.float))
         self.criterion = nn.CrossEntropyLoss(weight=weight, ignore_index=ignore_label, reduction="none")
@@ -184,9 +224,10 @@ class Dice(_AuxWeighted):
 
 
 def get_loss(loss_fn_name: str = "CrossEntropy", ignore_label: int = 255, cls_weights: Tensor = None,
-             native: bool = False):
+             native: bool = False, up_kernel: str = "gather"):
     assert loss_fn_name in __all__, f"Unavailable loss function name >> {loss_fn_name}.\nAvailable loss functions: {__all__}"
     if loss_fn_name == "Dice":
         return Dice()
     return {"CrossEntropy": CrossEntropy, "OhemCrossEntropy": OhemCrossEntropy}[loss_fn_name](ignore_label, cls_weights,
-                                                                                        native=native)
+                                                                                        native=native,
+                                                                                        up_kernel=up_kernel)

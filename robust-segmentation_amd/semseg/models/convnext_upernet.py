@@ -88,6 +88,9 @@ TRAIN_NATIVE_BLOCKS = os.environ.get("SEA_TRAIN_BLOCKS", "0") not in ("", "0")
 # interpolates inside its kernels; the full-resolution logits are never created and forward returns (loss, None).
 # Read once at import; tools/train_rob_seg.py --fused-criterion sets it for a run.
 TRAIN_FUSED_CRITERION = os.environ.get("SEA_TRAIN_FUSED_LOSS", "0") not in ("", "0")
+# T2u's kernel for that branch (semseg.losses: up_kernel): "gather", or "pow2" = forward and gradient in one pass for the
+# x4 main head and the x16 auxiliary head (csrc/train_loss_up_pow2.hip)
+TRAIN_FUSED_KERNEL = os.environ.get("SEA_TRAIN_FUSED_KERNEL", "gather")
 
 
 class _LayerNormHipTrain(torch.autograd.Function):
@@ -1551,15 +1554,16 @@ def _head_init(m):
             m.bias.data.zero_()
 
 
-_FUSED_CRITERION = []
+_FUSED_CRITERION = {}
 
 
 def _fused_criterion():
-    """the criterion of the fused training branch: F.cross_entropy(ignore_index=-1) on the device through T2u"""
-    if not _FUSED_CRITERION:
+    """the criterion of the fused training branch: F.cross_entropy(ignore_index=-1) on the device through T2u, with the
+    kernel TRAIN_FUSED_KERNEL names"""
+    if TRAIN_FUSED_KERNEL not in _FUSED_CRITERION:
         from ..losses import CrossEntropy
-        _FUSED_CRITERION.append(CrossEntropy(ignore_label=-1, native=True))
-    return _FUSED_CRITERION[0]
+        _FUSED_CRITERION[TRAIN_FUSED_KERNEL] = CrossEntropy(ignore_label=-1, native=True, up_kernel=TRAIN_FUSED_KERNEL)
+    return _FUSED_CRITERION[TRAIN_FUSED_KERNEL]
 
 
 class UperNetForSemanticSegmentation(nn.Module):

@@ -303,7 +303,12 @@ class SegMenter(nn.Module):
         x = x[:, 0 if "SAM" in self.backbone else 1 + int(self.encoder.distilled):]
         return self.decoder(x, (H0, W0)).contiguous(), (H0, W0)
 
-    def forward(self, im):
+    def forward(self, im, lowres=False):
+        """``lowres=True``: what ``forward_lowres(im)[0]`` returns, the masks at 1/16 resolution or None when the input would
+        need padding; the hook for a criterion that up-samples inside its kernels, reachable through a DDP wrapper."""
+        if lowres:
+            out = self.forward_lowres(im)
+            return None if out is None else out[0]
         H0, W0 = im.shape[2:]
         ph, pw = (-H0) % self.patch_size, (-W0) % self.patch_size
         if ph or pw:

@@ -24,7 +24,9 @@ warm-up (SCHEDULER is ignored).  Its crops satisfy (H - 1) % 8 == 0.
 ``--native-blocks`` runs the fp32 outer step's ConvNeXt trunk in NHWC on libsea_hip for this run (T3: LayerNorm with
 parameter gradients, fused stochastic-depth tail; ``semseg.models.convnext_upernet.TRAIN_NATIVE_BLOCKS``).
 ``--fused-criterion`` fuses the UperNet branch's final up-sampling into its two cross-entropies for this run (T2u;
-``semseg.models.convnext_upernet.TRAIN_FUSED_CRITERION``).
+``semseg.models.convnext_upernet.TRAIN_FUSED_CRITERION``), and the Segmenter branch's into its one (the model's masks at 1/16
+resolution through ``SegMenter.forward(im, lowres=True)``); ``--fused-kernel pow2`` runs them on the single-pass x4 / x16 kernel
+(``TRAIN_FUSED_KERNEL``).
 """
 from __future__ import annotations
 
@@ -129,6 +131,26 @@ def build_criterion(cfg, native: bool):
     return get_loss(cfg.get("LOSS", {}).get("NAME", "CrossEntropy"), -1, None, native=True)
 
 
+def build_fused_criterion(up_kernel: str = "gather"):
+    """--fused-criterion, Segmenter branch: F.cross_entropy(ignore_index=-1) whose ``upsampled`` takes the masks at 1/16
+    resolution and interpolates inside its kernels (T2u; ``up_kernel``: semseg.losses)."""
+    from semseg.losses import CrossEntropy
+    return CrossEntropy(-1, native=True, up_kernel=up_kernel)
+
+
+def segmenter_loss(ddp, img, lbl, criterion=None, fused=None):
+    """The Segmenter branch's outer loss (train_rob_seg.py:346-347).  ``fused`` (build_fused_criterion): the model's
+    low-resolution masks go straight into the criterion, no (B, C, H, W) tensor exists; a model that returns None (an input
+    that needs padding) takes the unfused line.  ``criterion`` (build_criterion): T2 on the full-resolution logits."""
+    if fused is not None:
+        low = ddp(img, lowres=True)
+        if low is not None:
+            return fused.upsampled(low, lbl)
+    if criterion is not None:
+        return criterion(ddp(img).contiguous(), lbl)
+    return torch.nn.functional.cross_entropy(ddp(img), lbl, ignore_index=-1)
+
+
 def _main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--cfg", type=str, default="configs/ade20k_convnext.yaml")
@@ -154,14 +176,18 @@ def _main(argv=None):
                     help="ConvNeXt trunk: train-mode blocks and trainable LayerNorms in NHWC on libsea_hip (T3, fp32; "
                          "csrc/ln_kernels.hip, csrc/block_tail.hip) for this run")
     ap.add_argument("--fused-criterion", action="store_true",
-                    help="UperNet branch: the outer step's cross-entropies take the heads' 1/4-resolution logits and "
-                         "interpolate inside the criterion (T2u, csrc/train_loss_up.hip) for this run; no "
-                         "full-resolution logits are created")
+                    help="UperNet and Segmenter branches: the outer step's cross-entropies take the heads' low-resolution "
+                         "logits (1/4 and 1/16; Segmenter's masks at 1/16) and interpolate inside the criterion (T2u, "
+                         "csrc/train_loss_up.hip) for this run; no full-resolution logits are created")
+    ap.add_argument("--fused-kernel", choices=("gather", "pow2"), default="gather",
+                    help="with --fused-criterion: T2u's kernel.  gather = any ratio, two launches; pow2 = forward and "
+                         "gradient in one pass for x4 / x16 (csrc/train_loss_up_pow2.hip)")
     args = ap.parse_args(argv)
     if args.native_blocks:
         _convnext.TRAIN_NATIVE_BLOCKS = True
     if args.fused_criterion:
         _convnext.TRAIN_FUSED_CRITERION = True
+        _convnext.TRAIN_FUSED_KERNEL = args.fused_kernel
     with open(args.cfg) as f:
         cfg = yaml.load(f, Loader=yaml.SafeLoader)
     train_cfg, model_cfg, data_cfg = cfg["TRAIN"], cfg["MODEL"], cfg["DATASET"]
@@ -226,6 +252,9 @@ def _main(argv=None):
     criterion = build_criterion(cfg, args.native_criterion)
     if criterion is not None:
         criterion = criterion.to(dev)
+    fused = None
+    if args.fused_criterion and model_cfg["NAME"] == "SegMenter":
+        fused = build_fused_criterion(args.fused_kernel).to(dev)
 
     def one_step(i):
         idx = [(i * bs + j) % n for j in range(bs)]
@@ -254,10 +283,8 @@ def _main(argv=None):
                     loss = main_loss + 0.4 * aux_loss
                 elif model_cfg["NAME"] == "UperNetForSemanticSegmentation":
                     loss, _ = ddp(img, lbl)
-                elif criterion is not None:
-                    loss = criterion(ddp(img).contiguous(), lbl)
                 else:
-                    loss = torch.nn.functional.cross_entropy(ddp(img), lbl, ignore_index=-1)
+                    loss = segmenter_loss(ddp, img, lbl, criterion, fused)
             # DDP all-reduces (averages) the gradient buckets in backward: the step's only collective.  Emulated
             # ranks accumulate loss / virt instead, which is the same average.
             (loss / virt if virt > 1 else loss).backward()
@@ -293,6 +320,7 @@ def _main(argv=None):
                "ms_per_outer_step": dt * 1e3 / args.steps, "last_loss": float(loss)}
         out["native_blocks"] = bool(_convnext.TRAIN_NATIVE_BLOCKS)
         out["fused_criterion"] = bool(_convnext.TRAIN_FUSED_CRITERION)
+        out["fused_kernel"] = _convnext.TRAIN_FUSED_KERNEL if _convnext.TRAIN_FUSED_CRITERION else None
         print(json.dumps(out))
         if args.json:
             json.dump(out, open(args.json, "w"))
@@ -311,13 +339,14 @@ def main(argv=None):
     that runs this in-process (tests do) must not inherit `cudnn.benchmark = True` or the T3 switch.  Returns rank 0's
     result record (the JSON line it prints)."""
     prev, prev_blocks = torch.backends.cudnn.benchmark, _convnext.TRAIN_NATIVE_BLOCKS
-    prev_fused = _convnext.TRAIN_FUSED_CRITERION
+    prev_fused, prev_kernel = _convnext.TRAIN_FUSED_CRITERION, _convnext.TRAIN_FUSED_KERNEL
     try:
         return _main(argv)
     finally:
         torch.backends.cudnn.benchmark = prev
         _convnext.TRAIN_NATIVE_BLOCKS = prev_blocks
         _convnext.TRAIN_FUSED_CRITERION = prev_fused
+        _convnext.TRAIN_FUSED_KERNEL = prev_kernel
 
 
 if __name__ == "__main__":
