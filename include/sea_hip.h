@@ -510,6 +510,8 @@ int sea_attention_bwd_f16(const float* q, const float* k, const float* v, int64_
  *   MFMAs (two blocks per CU), SEA_GEMM_PIPE_BIG = the one-block-per-CU 256 x 256 / 128 x 384 kernels wherever they apply.
  *   Same split and same MFMA order: every pipeline gives the same bits.  | SEA_GEMM_SHAPE16 = v_mfma_f32_16x16x32_* fragments
  *   (single-stage loop only; last bits differ: summation order).  Any other bit -> invalid argument.
+ *   The whole map from (shape, strides, terms, prologue / epilogue, word) to kernel, template parameters, grid and LDS bytes
+ *   is the one host function of csrc/gemm_plan.h; sea_gemm_plan below reports it without a launch.
  */
 #define SEA_GEMM_VARIANT_DEFAULT 0u
 #define SEA_GEMM_PIPE_SINGLE 1u
@@ -517,6 +519,15 @@ int sea_attention_bwd_f16(const float* q, const float* k, const float* v, int64_
 #define SEA_GEMM_PIPE_BIG 3u
 #define SEA_GEMM_PIPE_MASK 3u
 #define SEA_GEMM_SHAPE16 4u
+/* host only, touches no device: the kernel a sea_gemm_split* call with these integers runs (csrc/gemm_plan.h).  terms 1 | 2 |
+ * 3 | 22; ld_addend: SeaGemmEpilogue.ld_addend (0 without); prologue: 0 none, 1 a_gelu_grad_of, 2 a_gelu, 3 a_gelu_grad_of as
+ * a_gate; fused: addend, gelu_out or gelu_grad_of given.  Returns what the call would return for them (0, or 1 = invalid
+ * argument) and fills out = {kernel, terms_t, f16, s16, epi, pro, depth, bm, bn, npad, mblocks, nblocks, tiles, grid, threads,
+ * lds}: kernel 0 = single-stage, 1 = ping-pong, 2 = 256 x 256 tiles, 3 = 128 x 384 tiles (one block per CU); terms_t .. depth
+ * = the template parameters; bm x bn tiles, npad = rows of the packed weights, tiles = mblocks * nblocks * batch, grid =
+ * blocks (tiles rounded up to a multiple of 8), threads per block, lds = dynamic LDS bytes. */
+int sea_gemm_plan(int M, int N, int K, int terms, int batch, int64_t lda, int64_t ldc, int64_t ld_addend, int prologue, int fused,
+                  unsigned variant, int32_t out[16]);
 int64_t sea_gemm_split_packed_bytes(int N, int K, int terms);
 int sea_absmax_bits(const float* A, int64_t lda, int M, int K, int batch, int64_t strideA, int rows_per_word,
                     uint32_t* out_bits, void* stream);

@@ -1,7 +1,9 @@
 // Shared by gemm_split.hip (the three-blocks-per-CU kernel) and gemm_split_pp.hip (the ping-pong pipeline): operand-split
-// helpers, the LDS swizzle, the kernel argument block and the GELU formulas of M8.
+// helpers, the LDS swizzle, the kernel argument block and the GELU formulas of M8; and, with gemm_split_big.hip, how a launch
+// is made from a plan (gemm_plan.h): gemm_args_init, gemm_launch.
 #pragma once
 #include "sea_common.h"
+#include "gemm_plan.h"
 
 namespace sea {
 
@@ -141,7 +143,7 @@ __device__ __forceinline__ void gemm_split_store_tile(const GemmSplitArgs& p, co
                    (!(EPI && addg) || ((((ld_add | p.stride_add) & 3) == 0) && ((((uintptr_t)p.addend) & 15) == 0))) &&
                    (!(EPI && gelu_out) || ((((uintptr_t)p.gelu_out) & 15) == 0)) &&
                    (!(EPI && gelu_src) || ((((uintptr_t)p.gelu_grad_of) & 15) == 0));
-  const int off_c = lr * (int)ldc + col4;                     // (ldc < 2^28: checked by the launcher)
+  const int off_c = lr * (int)ldc + col4;                     // (ldc < 2^28: a condition of the plan)
   const int off_a = (EPI && addg) ? lr * (int)ld_add + col4 : 0;
   uint32_t omax = 0;
 #pragma unroll
@@ -219,10 +221,54 @@ __device__ __forceinline__ void gemm_split_store_tile(const GemmSplitArgs& p, co
   }
 }
 
-// launcher of the ping-pong kernel (gemm_split_pp.hip); returns false when the variant is not built for this mode
-bool gemm_split_pp_launch(const GemmSplitArgs& p, int terms, int pro, bool fused, hipStream_t st);
-// launcher of the one-block-per-CU kernels (gemm_split_big.hip): two terms, no fused extras; shape 0 = 256 x 256 tiles
-// (N % 256 == 0, no prologue), shape 1 = 128 x 384 tiles (N % 384 == 0, any prologue)
-bool gemm_split_big_launch(GemmSplitArgs p, int terms, int batch, int shape, int pro, hipStream_t st);
+// The fields every launch sets: operands, strides, the shape and the plan's geometry; with fp16 x 2 operands the inverse
+// weight scales sit behind the packed term images.  Everything else stays zero: the entry point that has it adds it.
+inline GemmSplitArgs gemm_args_init(const GemmPlan& pl, const float* A, int64_t lda, const void* Wp, float* C, int64_t ldc, int M,
+                                    int N, int K, int64_t strideA, int64_t strideW_bytes, int64_t strideC,
+                                    const uint32_t* amax_bits, int amax_rows) {
+  GemmSplitArgs p = {};
+  p.A = A;
+  p.W = (const char*)Wp;
+  p.C = C;
+  p.lda = lda;
+  p.ldc = ldc;
+  p.strideA = strideA;
+  p.strideW = strideW_bytes;
+  p.strideC = strideC;
+  p.M = M;
+  p.N = N;
+  p.K = K;
+  p.Npad = pl.npad;
+  p.mblocks = pl.mblocks;
+  p.nblocks = pl.nblocks;
+  p.total = pl.tiles;
+  p.per_xcd = pl.grid / 8;
+  p.amax_bits = amax_bits;
+  p.amax_rows = amax_rows;
+  p.amax_mul = 1.f;
+  p.w_inv = pl.f16 ? (const float*)((const char*)Wp + (int64_t)(K / GS_BK) * 2 * pl.npad * GS_BK * 2) : nullptr;
+  return p;
+}
+
+// Launches kernel KERN on the plan's grid.  More than 48 KB of dynamic LDS need an opt-in per kernel and device: made on the
+// first such launch (the flags are per instantiation of this function, that is per kernel), never in the per-call path.
+template <auto KERN, typename... Extra>
+inline void gemm_launch(const GemmSplitArgs& p, const GemmPlan& pl, hipStream_t st, Extra... extra) {
+  if (pl.lds > 48 * 1024) {
+    static bool attr_set_dev[64] = {};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (!attr_set_dev[dev & 63]) {
+      (void)hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+      attr_set_dev[dev & 63] = true;
+    }
+  }
+  hipLaunchKernelGGL(KERN, dim3(pl.grid), dim3(pl.threads), pl.lds, st, p, extra...);
+}
+
+// One launcher per file: maps the plan's template parameters to an instantiation and launches it.  They decide and check
+// nothing; SEA_ERR_ARG = a combination without instantiation, which gemm_plan never produces.
+int gemm_split_pp_launch(const GemmSplitArgs& p, const GemmPlan& pl, hipStream_t st);   // GEMM_PP (gemm_split_pp.hip)
+int gemm_split_big_launch(const GemmSplitArgs& p, const GemmPlan& pl, hipStream_t st);  // GEMM_BIG256 / _BIG384 (gemm_split_big.hip)
 
 }  // namespace sea

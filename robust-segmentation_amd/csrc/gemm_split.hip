@@ -560,26 +560,6 @@ using namespace sea;
 
 static inline int gs_npad(int N) { return (N + GS_BN - 1) / GS_BN * GS_BN; }
 
-// Smallest tile count for the 128 x 384 kernel: one round of one block per CU has to be at least three quarters full
-// (profiles/r5_gemm_wide_ab.md).
-static constexpr int kWideMin = 192;
-
-// The `variant` word of sea_gemm_split* (include/sea_hip.h): 0 = the shipped dispatch.  Bits 0-1 force a K-loop kernel, bit 2
-// the 16x16x32 fragments.  The kernels of every pipeline give the SAME BITS (same split, same MFMA order); the two fragment
-// shapes differ in the last bits (summation order).
-//   pipe 0 = the single-stage loop (32 KB of LDS, three blocks per CU), 1 = ping-pong (two LDS stages, one barrier per K step,
-//   the split in the MFMA shadow, loads two K steps ahead; two blocks per CU), 2 = per launch (shipped): the one-block-per-CU
-//   kernels and the ping-pong loop where they win IN the attack loop (see gemm_split_impl), 3 = the one-block-per-CU kernels
-//   wherever they apply.
-static inline int variant_pipe(unsigned variant) {
-  switch (variant & SEA_GEMM_PIPE_MASK) {
-    case SEA_GEMM_PIPE_SINGLE: return 0;
-    case SEA_GEMM_PIPE_PINGPONG: return 1;
-    case SEA_GEMM_PIPE_BIG: return 3;
-    default: return 2;
-  }
-}
-
 // terms: 3 / 2 = bf16 terms per operand; 22 = fp16 x 2 (22 significant bits, per-tensor power-of-two scaling)
 extern "C" int64_t sea_gemm_split_packed_bytes(int N, int K, int terms) {
   if (N <= 0 || K <= 0 || K % GS_BK || (terms != 1 && terms != 2 && terms != 3 && terms != 22)) return -1;
@@ -651,8 +631,6 @@ extern "C" int sea_gemm_split_fused(const float* A, int64_t lda, const void* Wp,
   if (epi) {
     SEA_CHECK_ARG(!epi->addend || epi->ld_addend >= N);
     SEA_CHECK_ARG(!(epi->gelu_out && epi->gelu_grad_of) && !(relu && (epi->gelu_out || epi->gelu_grad_of)));
-    SEA_CHECK_ARG(!(epi->a_gelu_grad_of || epi->a_gelu) || !(epi->addend || epi->gelu_out || epi->gelu_grad_of));
-    SEA_CHECK_ARG(!(epi->a_gelu_grad_of && epi->a_gelu));
   }
   return gemm_split_impl(A, lda, Wp, C, ldc, bias, relu, M, N, K, terms, batch, strideA, strideW_bytes, strideC,
                          terms == 22 ? amax_bits : nullptr, amax_rows, out_amax, variant, stream, epi);
@@ -710,105 +688,77 @@ extern "C" int sea_absmax_bits(const float* A, int64_t lda, int M, int K, int ba
   SEA_RETURN_LAST();
 }
 
+// Launch only: the single-stage kernel's instantiation and grid come from the plan (gemm_plan.h).  One case per instantiation:
+// every term count with both fragment shapes, plain / fused epilogue / the three prologues (three terms: GELU(A) only).
+static int gemm_split_single_launch(const GemmSplitArgs& p, const GemmPlan& pl, hipStream_t st) {
+  constexpr auto key = [](int terms, int s16, int f16, int epi, int pro) { return terms | s16 << 2 | f16 << 3 | epi << 4 | pro << 5; };
+#define SEA_GS_CASE(T, S16, F16, EPI, PRO) \
+  case key(T, S16, F16, EPI, PRO): gemm_launch<gemm_split_kernel<T, S16, F16, EPI, PRO>>(p, pl, st); return 0;
+#define SEA_GS_THREE(T, S16, F16) SEA_GS_CASE(T, S16, F16, false, 0) SEA_GS_CASE(T, S16, F16, true, 0) SEA_GS_CASE(T, S16, F16, false, 2)
+#define SEA_GS_MODES(T, S16, F16) SEA_GS_THREE(T, S16, F16) SEA_GS_CASE(T, S16, F16, false, 1) SEA_GS_CASE(T, S16, F16, false, 3)
+  switch (key(pl.terms_t, pl.s16, pl.f16, pl.epi, pl.pro)) {
+    SEA_GS_MODES(2, false, true) SEA_GS_MODES(2, true, true)
+    SEA_GS_MODES(2, false, false) SEA_GS_MODES(2, true, false)
+    SEA_GS_MODES(1, false, false) SEA_GS_MODES(1, true, false)   // one bf16 term: the operands of a bf16-autocast GEMM, fp32 in / out (BASELINE configs[3])
+    SEA_GS_THREE(3, false, false) SEA_GS_THREE(3, true, false)
+  }
+#undef SEA_GS_MODES
+#undef SEA_GS_THREE
+#undef SEA_GS_CASE
+  return SEA_ERR_ARG;
+}
+
 static int gemm_split_impl(const float* A, int64_t lda, const void* Wp, float* C, int64_t ldc, const float* bias, int relu, int M,
                            int N, int K, int terms, int batch, int64_t strideA, int64_t strideW_bytes, int64_t strideC,
                            const uint32_t* amax_bits, int amax_rows, uint32_t* out_amax, unsigned variant, void* stream,
                            const SeaGemmEpilogue* epi) {
-  SEA_CHECK_ARG((variant & ~(unsigned)(SEA_GEMM_PIPE_MASK | SEA_GEMM_SHAPE16)) == 0);
-  SEA_CHECK_ARG(A && Wp && C && M > 0 && N > 0 && K > 0 && (K % GS_BK) == 0 && batch > 0);
-  SEA_CHECK_ARG(lda >= K && ldc >= N && (lda % 4) == 0 && (int64_t)M * lda < (1ll << 30));  // 32-bit lane offsets into A
+  SEA_CHECK_ARG(A && Wp && C);
   SEA_CHECK_ARG(((((uintptr_t)A) | ((uintptr_t)Wp)) & 15) == 0 && (((uintptr_t)C) & 3) == 0 && (strideA % 4) == 0 &&
                 (strideW_bytes % 16) == 0);
-  GemmSplitArgs p = {};
-  p.A = A;
-  p.W = (const char*)Wp;
-  p.C = C;
+  const float* const a_t = epi ? epi->a_gelu_grad_of : nullptr;   // second operand of prologues 1 and 3
+  const bool a_gelu = epi && epi->a_gelu;
+  SEA_CHECK_ARG(!(a_gelu && a_t) && (((uintptr_t)a_t) & 15) == 0);
+  // which kernel, which instantiation, which grid: the plan's business, with every check that depends on integers only
+  const int pro = a_gelu ? 2 : (a_t ? (epi->a_gate ? 3 : 1) : 0);
+  const bool fused = epi && (epi->addend || epi->gelu_out || epi->gelu_grad_of);
+  GemmPlan pl;
+  SEA_CHECK_ARG(gemm_plan(GemmQuery{M, N, K, terms, batch, lda, ldc, epi ? epi->ld_addend : 0, pro, fused, variant}, &pl) == 0);
+  GemmSplitArgs p = gemm_args_init(pl, A, lda, Wp, C, ldc, M, N, K, strideA, strideW_bytes, strideC, amax_bits, amax_rows);
   p.bias = bias;
-  p.lda = lda;
-  p.ldc = ldc;
-  p.strideA = strideA;
-  p.strideW = strideW_bytes;
-  p.strideC = strideC;
-  p.M = M;
-  p.N = N;
-  p.K = K;
-  p.Npad = gs_npad(N);
-  p.mblocks = (M + GS_BM - 1) / GS_BM;
-  p.nblocks = p.Npad / GS_BN;
-  const int64_t total = (int64_t)p.mblocks * p.nblocks * batch;
-  SEA_CHECK_ARG(total < (1ll << 30));
-  p.total = (int)total;
-  p.per_xcd = (p.total + 7) / 8;
   p.relu = relu;
-  p.amax_bits = amax_bits;
-  p.amax_rows = amax_rows;
   p.out_amax = out_amax;
-  p.addend = epi ? epi->addend : nullptr;
-  p.ld_add = epi ? epi->ld_addend : 0;
-  p.stride_add = epi ? epi->stride_addend : 0;
-  p.gelu_out = epi ? epi->gelu_out : nullptr;
-  p.gelu_grad_of = epi ? epi->gelu_grad_of : nullptr;
-  p.a_gelu_grad_of = epi ? epi->a_gelu_grad_of : nullptr;
-  p.a_gelu = epi ? epi->a_gelu : 0;
-  p.a_gate = epi ? epi->a_gate : 0;
-  p.amax_mul = (epi && epi->a_amax_mul > 0.f) ? epi->a_amax_mul : 1.f;
-  p.amax_mul_dev = epi ? epi->a_amax_mul_dev : nullptr;
-  p.w_inv = terms == 22 ? (const float*)((const char*)Wp + (int64_t)(K / GS_BK) * 2 * gs_npad(N) * GS_BK * 2) : nullptr;
-  const dim3 grid(p.per_xcd * 8), block(256);
-  // MFMA shape: 32x32x16 fragments (default) or 16x16x32 (variant bit SEA_GEMM_SHAPE16): the chip holds a
-  // higher clock on the small shape in MFMA-dense loops (MI355X guide, DVFS give-back item 7); which one wins is measured
-  // IN the attack loop, where the clock is the limiter (profiles/r4_rejected_experiments.md: +3.6 % per step on the small shape)
-  const bool shape16 = (variant & SEA_GEMM_SHAPE16) != 0;
-  const bool fused = p.addend || p.gelu_out || p.gelu_grad_of;
-  SEA_CHECK_ARG(!(p.a_gelu && (fused || p.a_gelu_grad_of)) && (!p.a_gelu_grad_of || !fused));
-  SEA_CHECK_ARG(!p.a_gelu_grad_of || ((terms == 1 || terms == 2 || terms == 22) && (((uintptr_t)p.a_gelu_grad_of) & 15) == 0));
-  // prologue: 0 none, 1 A * GELU'(t), 2 GELU(A), 3 ReLU gate
-  const int pro = p.a_gelu ? 2 : (p.a_gelu_grad_of ? (p.a_gate ? 3 : 1) : 0);
+  if (epi) {
+    p.addend = epi->addend;
+    p.ld_add = epi->ld_addend;
+    p.stride_add = epi->stride_addend;
+    p.gelu_out = epi->gelu_out;
+    p.gelu_grad_of = epi->gelu_grad_of;
+    p.a_gelu_grad_of = a_t;
+    p.a_gelu = epi->a_gelu;
+    p.a_gate = epi->a_gate;
+    if (epi->a_amax_mul > 0.f) p.amax_mul = epi->a_amax_mul;
+    p.amax_mul_dev = epi->a_amax_mul_dev;
+  }
   const hipStream_t st = (hipStream_t)stream;
-  const int pipe = variant_pipe(variant);
-  // One-block-per-CU kernels (gemm_split_big.hip) for the products that are bound by the bytes a CU pulls through its L1.
-  // pipe 3 forces them wherever they apply; pipe 2 takes 256 x 256 tiles from 1024 tiles on (the Winograd-domain products) and
-  // 128 x 384 tiles where they fill the chip in whole rounds (256 CUs: the 32 x 32-pixel stage's M = 8192 products).
-  if (!shape16 && (terms == 22 || terms == 2) && !fused && (pipe == 2 || pipe == 3)) {
-    const int64_t t256 = (N % 256) == 0 ? (int64_t)((M + 255) / 256) * (N / 256) * batch : 0;
-    const int64_t t384 = (N % 384) == 0 ? (int64_t)((M + 127) / 128) * (N / 384) * batch : 0;
-    if (pro == 0 && M >= 256 && t256 > 0 && (pipe == 3 ? t384 == 0 : t256 >= 1024) && gemm_split_big_launch(p, terms, batch, 0, 0, st))
-      SEA_RETURN_LAST();
-    // (one round of one block per CU: measured in the loop -- 39 / 48 / 45 us against 41 / 61 / 50 us for the plain / GELU' /
-    // GELU launches of the M = 8192 products; on two or more rounds the 128 x 128 kernels win, profiles/r5_gemm_wide_ab.md)
-    const bool wide_fits = t384 >= kWideMin && t384 <= 256 && K >= 192;
-    if (t384 > 0 && M >= 128 && (pipe == 3 || wide_fits) && gemm_split_big_launch(p, terms, batch, 1, pro, st)) SEA_RETURN_LAST();
+  int rc;
+  switch (pl.kernel) {
+    case GEMM_BIG256:
+    case GEMM_BIG384: rc = gemm_split_big_launch(p, pl, st); break;
+    case GEMM_PP: rc = gemm_split_pp_launch(p, pl, st); break;
+    default: rc = gemm_split_single_launch(p, pl, st); break;
   }
-  // per launch (pipe 2): the ping-pong kernel where it wins IN the attack loop (profiles/r5_gemm_pipe_ab.md): a VALU-heavy
-  // prologue (GELU / GELU' / gate on A: hidden in its MFMA shadow) on a grid that fills two blocks per CU at least as
-  // well as three (768 tiles are one round of three blocks per CU but one and a half of two)
-  const int64_t r2 = (total + 511) / 512 * 512, r3 = (total + 767) / 768 * 768;
-  const bool pingpong = pipe == 1 || (pipe == 2 && pro != 0 && r2 <= r3);
-  if (!shape16 && terms != 3 && pingpong && gemm_split_pp_launch(p, terms, pro, fused, st)) SEA_RETURN_LAST();
-#define SEA_GS_LAUNCH(T, S16, F16, EPI, PRO) hipLaunchKernelGGL((gemm_split_kernel<T, S16, F16, EPI, PRO>), grid, block, 0, st, p)
-#define SEA_GS_PRO(T, S16, F16)                                   \
-  do {                                                            \
-    if (pro == 2) SEA_GS_LAUNCH(T, S16, F16, false, 2);           \
-    else if (pro == 1) SEA_GS_LAUNCH(T, S16, F16, false, 1);      \
-    else if (pro == 3) SEA_GS_LAUNCH(T, S16, F16, false, 3);      \
-    else if (fused) SEA_GS_LAUNCH(T, S16, F16, true, 0);          \
-    else SEA_GS_LAUNCH(T, S16, F16, false, 0);                    \
-  } while (0)
-  if (terms == 22) {
-    if (shape16) SEA_GS_PRO(2, true, true); else SEA_GS_PRO(2, false, true);
-  } else if (terms == 3) {
-    SEA_CHECK_ARG(pro == 0 || pro == 2);
-    if (shape16) {
-      if (pro == 2) SEA_GS_LAUNCH(3, true, false, false, 2); else if (fused) SEA_GS_LAUNCH(3, true, false, true, 0); else SEA_GS_LAUNCH(3, true, false, false, 0);
-    } else {
-      if (pro == 2) SEA_GS_LAUNCH(3, false, false, false, 2); else if (fused) SEA_GS_LAUNCH(3, false, false, true, 0); else SEA_GS_LAUNCH(3, false, false, false, 0);
-    }
-  } else if (terms == 1) {   // one bf16 term: the operands of a bf16-autocast GEMM, fp32 in / out (BASELINE configs[3])
-    if (shape16) SEA_GS_PRO(1, true, false); else SEA_GS_PRO(1, false, false);
-  } else {
-    if (shape16) SEA_GS_PRO(2, true, false); else SEA_GS_PRO(2, false, false);
-  }
-#undef SEA_GS_PRO
-#undef SEA_GS_LAUNCH
+  SEA_CHECK_ARG(rc == 0);
   SEA_RETURN_LAST();
+}
+
+// host only: the plan of a call, without the call
+extern "C" int sea_gemm_plan(int M, int N, int K, int terms, int batch, int64_t lda, int64_t ldc, int64_t ld_addend, int prologue,
+                             int fused, unsigned variant, int32_t out[16]) {
+  SEA_CHECK_ARG(out != nullptr);
+  GemmPlan p;
+  const int rc = gemm_plan(GemmQuery{M, N, K, terms, batch, lda, ldc, ld_addend, prologue, fused != 0, variant}, &p);
+  const int v[16] = {p.kernel, p.terms_t, p.f16, p.s16, p.epi, p.pro, p.depth, p.bm, p.bn, p.npad, p.mblocks, p.nblocks, p.tiles, p.grid,
+                     p.threads, (int)p.lds};
+  for (int i = 0; i < 16; ++i) out[i] = v[i];
+  return rc;
 }

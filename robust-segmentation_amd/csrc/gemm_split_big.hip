@@ -441,51 +441,26 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_split_big_kernel(const Gemm
 #endif
 }
 
-template <bool F16, int WM, int WN, int TN, int PRO, int DEPTH, int KO = 0, bool STAMP = false>
-static void big_launch_one(const GemmSplitArgs& p SEA_BIG_DIAG_PARAM, hipStream_t st) {
-  constexpr int lds = 2 * 65536 + 2 * 64 * WM * (int)sizeof(float);
-  auto k = gemm_split_big_kernel<F16, WM, WN, TN, PRO, DEPTH, KO, STAMP>;
-  static bool attr_set_dev[64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (!attr_set_dev[dev & 63]) {
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set_dev[dev & 63] = true;
-  }
-  hipLaunchKernelGGL(k, dim3(p.per_xcd * 8), dim3(64 * WM * WN), (size_t)lds, st, p SEA_BIG_DIAG_ARG);
-}
-
-// launches a one-block-per-CU kernel; the caller has checked: terms 22 or 2, no fused epilogue extras.
-// shape 0: 256 x 256 tiles (N % 256 == 0, no prologue); shape 1: 128 x 384 tiles (N % 384 == 0, any prologue)
-bool gemm_split_big_launch(GemmSplitArgs p, int terms, int batch, int shape, int pro, hipStream_t st) {
-  const int BM = shape ? 128 : 256, BN = shape ? 384 : 256;
-  if (p.ldc >= (1ll << 28) || p.lda >= (1ll << 22) || (p.N % BN) != 0 || p.Npad < p.N || (p.Npad % 128) != 0 || (shape == 0 && pro != 0))
-    return false;
-  if (p.Npad % BN) return false;                         // (a tile's weight rows must exist in the packed image)
-  p.mblocks = (p.M + BM - 1) / BM;
-  p.nblocks = p.N / BN;
-  const int64_t total = (int64_t)p.mblocks * p.nblocks * batch;
-  if (total >= (1ll << 30)) return false;
-  p.total = (int)total;
-  p.per_xcd = (p.total + 7) / 8;
-  const bool f16 = terms == 22;
+// Launch only: instantiation, grid and LDS bytes come from the plan (gemm_plan.h).  256 x 256 tiles: waves 4 x 2, wave tile
+// 64 x 128; 128 x 384 tiles: waves 2 x 4, wave tile 64 x 96.  One case per instantiation.
+int gemm_split_big_launch(const GemmSplitArgs& p, const GemmPlan& pl, hipStream_t st) {
 #ifdef SEA_GEMM_BIG_DIAG
   const BigDiag dg = {0, 0, nullptr};
 #endif
-  if (shape == 0) {
-    if (f16) big_launch_one<true, 4, 2, 4, 0, 1>(p SEA_BIG_DIAG_ARG, st); else big_launch_one<false, 4, 2, 4, 0, 1>(p SEA_BIG_DIAG_ARG, st);
-    return true;
+  constexpr auto key = [](int wide, int f16, int pro, int depth) { return wide | f16 << 1 | pro << 2 | depth << 4; };
+#define SEA_BIG_CASE(WIDE, F16, PRO, DEPTH)  \
+  case key(WIDE, F16, PRO, DEPTH):           \
+    gemm_launch<gemm_split_big_kernel<F16, WIDE ? 2 : 4, WIDE ? 4 : 2, WIDE ? 3 : 4, PRO, DEPTH>>(p, pl, st SEA_BIG_DIAG_ARG); \
+    return 0;
+#define SEA_BIG_MODES(F16) \
+  SEA_BIG_CASE(0, F16, 0, 1) SEA_BIG_CASE(1, F16, 0, 2) SEA_BIG_CASE(1, F16, 1, 1) SEA_BIG_CASE(1, F16, 2, 2) SEA_BIG_CASE(1, F16, 3, 1)
+  switch (key(pl.kernel == GEMM_BIG384, pl.f16, pl.pro, pl.depth)) {
+    SEA_BIG_MODES(true)
+    SEA_BIG_MODES(false)
   }
-#define SEA_BIG_WIDE(F)                                              \
-  do {                                                               \
-    if (pro == 0) big_launch_one<F, 2, 4, 3, 0, 2>(p SEA_BIG_DIAG_ARG, st);       \
-    else if (pro == 1) big_launch_one<F, 2, 4, 3, 1, 1>(p SEA_BIG_DIAG_ARG, st);  \
-    else if (pro == 2) big_launch_one<F, 2, 4, 3, 2, 2>(p SEA_BIG_DIAG_ARG, st);  \
-    else big_launch_one<F, 2, 4, 3, 3, 1>(p SEA_BIG_DIAG_ARG, st);                \
-  } while (0)
-  if (f16) SEA_BIG_WIDE(true); else SEA_BIG_WIDE(false);
-#undef SEA_BIG_WIDE
-  return true;
+#undef SEA_BIG_MODES
+#undef SEA_BIG_CASE
+  return SEA_ERR_ARG;
 }
 
 #ifdef SEA_GEMM_BIG_DIAG
@@ -494,13 +469,9 @@ bool gemm_split_big_launch(GemmSplitArgs p, int terms, int batch, int shape, int
 extern "C" int sea_gemm_big_diag(const float* A, int64_t lda, const void* Wp, float* C, int64_t ldc, int M, int N, int K, int batch,
                                  int64_t strideA, int64_t strideW_bytes, int64_t strideC, const uint32_t* amax_bits, int amax_rows,
                                  int ko, int step_ticks, unsigned long long* stamps, void* stream) {
-  if (M <= 0 || N <= 0 || (N % 256) != 0 || K <= 0 || (K % GS_BK) != 0 || lda >= (1ll << 22) || ldc >= (1ll << 28)) return 1;
-  GemmSplitArgs p = {};
-  p.A = A; p.W = (const char*)Wp; p.C = C; p.lda = lda; p.ldc = ldc; p.strideA = strideA; p.strideW = strideW_bytes; p.strideC = strideC;
-  p.M = M; p.N = N; p.K = K; p.Npad = N;
-  p.mblocks = (M + 255) / 256; p.nblocks = N / 256; p.total = p.mblocks * p.nblocks * batch; p.per_xcd = (p.total + 7) / 8;
-  p.amax_bits = amax_bits; p.amax_rows = amax_rows; p.amax_mul = 1.f;
-  p.w_inv = (const float*)((const char*)Wp + (int64_t)(K / GS_BK) * 2 * p.Npad * GS_BK * 2);
+  GemmPlan pl;   // the plan of the plain fp16 x 2 product with the one-block-per-CU kernels forced: only where that is 256 x 256
+  if (gemm_plan(GemmQuery{M, N, K, 22, batch, lda, ldc, 0, 0, false, SEA_GEMM_PIPE_BIG}, &pl) != 0 || pl.kernel != GEMM_BIG256) return 1;
+  const GemmSplitArgs p = gemm_args_init(pl, A, lda, Wp, C, ldc, M, N, K, strideA, strideW_bytes, strideC, amax_bits, amax_rows);
   int dev = 0, cus = 0;
   (void)hipGetDevice(&dev);
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 1;
@@ -510,17 +481,12 @@ extern "C" int sea_gemm_big_diag(const float* A, int64_t lda, const void* Wp, fl
     dg.step_ticks = step_ticks;
   }
   const hipStream_t st = (hipStream_t)stream;
-  if (stamps) {
-    if (ko == 0) big_launch_one<true, 4, 2, 4, 0, 1, 0, true>(p SEA_BIG_DIAG_ARG, st);
-    else if (ko == 1) big_launch_one<true, 4, 2, 4, 0, 1, 1, true>(p SEA_BIG_DIAG_ARG, st);
-    else if (ko == 64) big_launch_one<true, 4, 2, 4, 0, 1, 64, true>(p SEA_BIG_DIAG_ARG, st);
-    else return 1;
-  } else {
-    if (ko == 0) big_launch_one<true, 4, 2, 4, 0, 1>(p SEA_BIG_DIAG_ARG, st);
-    else if (ko == 1) big_launch_one<true, 4, 2, 4, 0, 1, 1>(p SEA_BIG_DIAG_ARG, st);
-    else if (ko == 64) big_launch_one<true, 4, 2, 4, 0, 1, 64>(p SEA_BIG_DIAG_ARG, st);
-    else return 1;
-  }
+#define SEA_BIG_KO(KO, STAMP) gemm_launch<gemm_split_big_kernel<true, 4, 2, 4, 0, 1, KO, STAMP>>(p, pl, st, dg)
+  if (ko == 0) { if (stamps) SEA_BIG_KO(0, true); else SEA_BIG_KO(0, false); }
+  else if (ko == 1) { if (stamps) SEA_BIG_KO(1, true); else SEA_BIG_KO(1, false); }
+  else if (ko == 64) { if (stamps) SEA_BIG_KO(64, true); else SEA_BIG_KO(64, false); }
+  else return 1;
+#undef SEA_BIG_KO
   return (int)hipGetLastError();
 }
 #endif

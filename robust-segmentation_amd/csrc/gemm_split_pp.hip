@@ -339,78 +339,44 @@ __global__ __launch_bounds__(256, 2) void gemm_split_pp_kernel(const GemmSplitAr
   gemm_split_store_tile<F16, EPI, KO>(p, acc, g, m0, n0, smem, row_inv, bv_c, wi_c);
 }
 
-template <int TERMS, bool F16, bool EPI, int PRO, int DEPTH>
-static void pp_launch_one(const GemmSplitArgs& p, hipStream_t st) {
-  constexpr int lds = 2 * 2 * TERMS * GS_IMG + (F16 ? 2 * GS_BM * (int)sizeof(float) : 0);
-  auto k = gemm_split_pp_kernel<TERMS, F16, EPI, PRO, DEPTH>;
-  if (lds > 48 * 1024) {   // opt in once per device
-    static bool attr_set_dev[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!attr_set_dev[dev & 63]) {
-      (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      attr_set_dev[dev & 63] = true;
-    }
+// Launch only: instantiation, grid and LDS bytes come from the plan (gemm_plan.h).  One case per instantiation.
+int gemm_split_pp_launch(const GemmSplitArgs& p, const GemmPlan& pl, hipStream_t st) {
+  constexpr auto key = [](int terms, int f16, int epi, int pro, int depth) { return terms | f16 << 2 | epi << 3 | pro << 4 | depth << 6; };
+#define SEA_PP_CASE(T, F16, EPI, PRO, DEPTH) \
+  case key(T, F16, EPI, PRO, DEPTH): gemm_launch<gemm_split_pp_kernel<T, F16, EPI, PRO, DEPTH>>(p, pl, st); return 0;
+#define SEA_PP_MODES(T, F16) \
+  SEA_PP_CASE(T, F16, false, 0, 2) SEA_PP_CASE(T, F16, true, 0, 2) SEA_PP_CASE(T, F16, false, 1, 1) SEA_PP_CASE(T, F16, false, 2, 2) SEA_PP_CASE(T, F16, false, 3, 1)
+  switch (key(pl.terms_t, pl.f16, pl.epi, pl.pro, pl.depth)) {
+    SEA_PP_MODES(2, true)
+    SEA_PP_MODES(2, false)
+    SEA_PP_MODES(1, false)
   }
-  hipLaunchKernelGGL(k, dim3(p.per_xcd * 8), dim3(256), (size_t)lds, st, p);
-}
-
-template <int TERMS, bool F16>
-static void pp_launch_mode(const GemmSplitArgs& p, int pro, bool fused, hipStream_t st) {
-  // the prologues with a second operand keep one register set (two would not fit 256 VGPRs next to 64 accumulators)
-  if (pro == 2) pp_launch_one<TERMS, F16, false, 2, 2>(p, st);
-  else if (pro == 1) pp_launch_one<TERMS, F16, false, 1, 1>(p, st);
-  else if (pro == 3) pp_launch_one<TERMS, F16, false, 3, 1>(p, st);
-  else if (fused) pp_launch_one<TERMS, F16, true, 0, 2>(p, st);
-  else pp_launch_one<TERMS, F16, false, 0, 2>(p, st);
+#undef SEA_PP_MODES
+#undef SEA_PP_CASE
+  return SEA_ERR_ARG;
 }
 
 #ifdef SEA_GEMM_KNOCKOUT
-template <int KO>
-static void ko_launch(const GemmSplitArgs& p, hipStream_t st) {
-  constexpr int lds = 2 * 2 * 2 * GS_IMG + 2 * GS_BM * (int)sizeof(float);
-  auto k = gemm_split_pp_kernel<2, true, false, 0, 2, KO>;
-  (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  hipLaunchKernelGGL(k, dim3(p.per_xcd * 8), dim3(256), (size_t)lds, st, p);
-}
 // timing-only launches of the fp16 x 2 ping-pong kernel with parts knocked out: ko bits 1 no C stores, 2 no A loads, 4 no W
 // loads (zero-record descriptors), 8 no MFMAs, 16 no LDS staging writes.  Results are garbage by construction.
 extern "C" int sea_gemm_pp_knockout(const float* A, int64_t lda, const void* Wp, float* C, int64_t ldc, int M, int N, int K, int batch,
                                     int64_t strideA, int64_t strideW_bytes, int64_t strideC, const uint32_t* amax_bits, int amax_rows,
                                     int ko, void* stream) {
-  GemmSplitArgs p = {};
-  p.A = A; p.W = (const char*)Wp; p.C = C; p.lda = lda; p.ldc = ldc; p.strideA = strideA; p.strideW = strideW_bytes; p.strideC = strideC;
-  p.M = M; p.N = N; p.K = K; p.Npad = (N + GS_BN - 1) / GS_BN * GS_BN;
-  p.mblocks = (M + GS_BM - 1) / GS_BM; p.nblocks = p.Npad / GS_BN; p.total = p.mblocks * p.nblocks * batch; p.per_xcd = (p.total + 7) / 8;
-  p.amax_bits = amax_bits; p.amax_rows = amax_rows; p.amax_mul = 1.f;
-  p.w_inv = (const float*)((const char*)Wp + (int64_t)(K / GS_BK) * 2 * p.Npad * GS_BK * 2);
+  GemmPlan pl;   // the plan of the plain fp16 x 2 product with the ping-pong loop forced
+  if (gemm_plan(GemmQuery{M, N, K, 22, batch, lda, ldc, 0, 0, false, SEA_GEMM_PIPE_PINGPONG}, &pl) != 0 || pl.kernel != GEMM_PP) return 1;
+  GemmSplitArgs p = gemm_args_init(pl, A, lda, Wp, C, ldc, M, N, K, strideA, strideW_bytes, strideC, amax_bits, amax_rows);
   p.ko = ko;
   const hipStream_t st = (hipStream_t)stream;
-  switch (ko & ~6) {   // bits 2 and 4 are run-time (descriptor sizes)
-    case 0: ko_launch<32>(p, st); break;     // (32: nothing compiled out, the run-time bits only)
-    case 1: ko_launch<1>(p, st); break;
-    case 8: ko_launch<8>(p, st); break;
-    case 9: ko_launch<9>(p, st); break;
-    case 16: ko_launch<16>(p, st); break;
-    case 24: ko_launch<24>(p, st); break;
-    case 25: ko_launch<25>(p, st); break;
-    case 64: ko_launch<64>(p, st); break;   // (64: non-temporal C stores)
-    case 72: ko_launch<72>(p, st); break;
-    case 128: ko_launch<128>(p, st); break;   // (128: no VALU split of A)
-    case 129: ko_launch<129>(p, st); break;
+#define SEA_KO_CASE(KO) case KO: gemm_launch<gemm_split_pp_kernel<2, true, false, 0, 2, KO ? KO : 32>>(p, pl, st); break;
+  switch (ko & ~6) {   // bits 2 and 4 are run-time (descriptor sizes); 0 runs as 32: nothing compiled out, the run-time bits only
+    SEA_KO_CASE(0) SEA_KO_CASE(1) SEA_KO_CASE(8) SEA_KO_CASE(9) SEA_KO_CASE(16) SEA_KO_CASE(24) SEA_KO_CASE(25)
+    SEA_KO_CASE(64) SEA_KO_CASE(72)     // (64: non-temporal C stores)
+    SEA_KO_CASE(128) SEA_KO_CASE(129)   // (128: no VALU split of A)
     default: return 1;
   }
+#undef SEA_KO_CASE
   return (int)hipGetLastError();
 }
 #endif
-
-bool gemm_split_pp_launch(const GemmSplitArgs& p, int terms, int pro, bool fused, hipStream_t st) {
-  if (p.ldc >= (1ll << 28) || p.ld_add >= (1ll << 28)) return false;
-  if (terms == 22) pp_launch_mode<2, true>(p, pro, fused, st);
-  else if (terms == 2) pp_launch_mode<2, false>(p, pro, fused, st);
-  else if (terms == 1) pp_launch_mode<1, false>(p, pro, fused, st);
-  else return false;
-  return true;
-}
 
 }  // namespace sea

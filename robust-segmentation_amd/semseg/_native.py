@@ -97,6 +97,7 @@ _SIGS = {
     "sea_gemm_split_packed_bytes": (_i64, [_i, _i, _i]),
     "sea_gemm_split_pack": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _vp]),
     "sea_gemm_split": (_i, [_vp, _i64, _vp, _vp, _i64, _vp, _i, _i, _i, _i, _i, _i, _i64, _i64, _i64, _u, _vp]),
+    "sea_gemm_plan": (_i, [_i, _i, _i, _i, _i, _i64, _i64, _i64, _i, _i, _u, C.POINTER(C.c_int32)]),
     "sea_mlp_fused_supported": (_i, [_i, _i]),
     "sea_classifier_supported": (_i, [_i, _i, _i]),
     "sea_classifier_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
@@ -1791,6 +1792,25 @@ def gemm_variant(pipe=None, mfma_shape=None) -> int:
     if pipe not in _GEMM_PIPE_BITS or mfma_shape not in (16, 32):
         raise SeaNativeError("gemm_split: pipe must be 0, 1, 2 or 3 and mfma_shape 16 or 32")
     return _GEMM_PIPE_BITS[pipe] | (_GEMM_SHAPE16 if mfma_shape == 16 else 0)
+
+
+GEMM_KERNELS = ("single", "pp", "big256", "big384")
+_GEMM_PLAN_FIELDS = ("kernel", "terms_t", "f16", "s16", "epi", "pro", "depth", "bm", "bn", "npad", "mblocks", "nblocks", "tiles",
+                     "grid", "threads", "lds")
+
+
+def gemm_plan(M: int, N: int, K: int, terms: int, batch: int = 1, lda=None, ldc=None, ld_add: int = 0, prologue: int = 0,
+              fused: bool = False, pipe=None, mfma_shape=None) -> dict:
+    """Which kernel ``sea_gemm_split*`` runs for these arguments (host only, no device; csrc/gemm_plan.h): dict(rc, kernel in
+    GEMM_KERNELS, the template parameters terms_t / f16 / s16 / epi / pro / depth, the geometry bm / bn / npad / mblocks /
+    nblocks / tiles / grid / threads / lds), ``rc`` = 1 where the call itself would be an invalid argument.  ``prologue``: 0
+    none, 1 ``a_gelu_grad_of``, 2 ``a_gelu``, 3 ``a_relu_gate``; ``fused``: an addend, ``gelu_out`` or ``gelu_grad_of``;
+    ``lda`` / ``ldc`` default to dense rows.  The split-K choice of ``gemm_split`` comes before this and is not part of it."""
+    out = (C.c_int32 * len(_GEMM_PLAN_FIELDS))()
+    rc = lib().sea_gemm_plan(M, N, K, terms, batch, K if lda is None else lda, N if ldc is None else ldc, ld_add, prologue,
+                             int(bool(fused)), gemm_variant(pipe, mfma_shape), out)
+    plan = dict(zip(_GEMM_PLAN_FIELDS, out), rc=rc)
+    return dict(plan, kernel=GEMM_KERNELS[plan["kernel"]], **{k: bool(plan[k]) for k in ("f16", "s16", "epi")})
 
 
 def gemm_split(A, Wp: PackedWeight, bias=None, relu: bool = False, out=None, amax=None, out_amax=None, addend=None,

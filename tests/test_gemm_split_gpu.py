@@ -556,6 +556,45 @@ def test_one_block_per_cu_kernels_give_the_bits_of_the_128x128_kernels(N, G, M, 
     assert (o3[22, "plain"].double() - ref).abs().max().item() <= 3e-6 * ref.abs().max().item()
 
 
+DEFAULT_DISPATCH_CASES = [   # (kernel, G, M, K, Nn, keyword of gemm_split or None, prologue of gemm_plan)
+    ("single", 1, 300, 96, 200, None, 0),
+    ("pp", 1, 300, 96, 200, "a_relu_gate", 3),
+    ("pp", 1, 300, 96, 200, "a_gelu_grad_of", 1),
+    ("single", 1, 8192, 96, 1536, "a_gelu", 2),         # 768 tiles (one and a half rounds of two blocks per CU), K < 192
+    ("big384", 1, 8192, 192, 1536, None, 0),            # t384 = 64 * 4 = 256
+    ("big384", 1, 8192, 192, 1536, "a_gelu_grad_of", 1),
+    ("big384", 1, 8192, 192, 1536, "a_gelu", 2),
+    ("big384", 1, 8192, 192, 1536, "a_relu_gate", 3),
+    ("big256", 4, 65536, 32, 256, None, 0),             # t256 = 256 * 1 * 4 = 1024
+    ("big256", 4, 65536, 32, 256, "bias_relu", 0),
+]
+
+
+@pytest.mark.parametrize("kernel,G,M,K,Nn,mode,pro", DEFAULT_DISPATCH_CASES)
+def test_default_dispatch_reaches_each_kernel_with_the_bits_of_the_single_stage_loop(N, kernel, G, M, K, Nn, mode, pro):
+    """The word without an override (pipe=None): csrc/gemm_plan.h names the expected kernel for the smallest shapes that take
+    each of its branches, and the call gives the bits of pipe=0, for fp16 x 2 and bf16 x 2.  (The tests above force the pipe.)"""
+    assert G > 1 or N._ksplit(M, Nn, K) == 1          # (no split-K in front of the plan)
+    g = torch.Generator(device="cuda").manual_seed(M + K + Nn + pro)
+    A = torch.randn(G, M, K, generator=g, device="cuda") * torch.exp2(torch.randint(-6, 3, (G, M, 1), generator=g, device="cuda").float())
+    W = torch.randn(G, Nn, K, generator=g, device="cuda") / K ** 0.5
+    kw = {}
+    if mode == "bias_relu":
+        kw = dict(bias=torch.randn(Nn, generator=g, device="cuda"), relu=True)
+    elif mode == "a_gelu":
+        kw = dict(a_gelu=True)
+    elif mode is not None:
+        kw = {mode: torch.randn(G, M, K, generator=g, device="cuda")}
+    if G == 1:
+        A, W, kw = A[0], W[0], {k: (v[0] if k.startswith("a_") and torch.is_tensor(v) else v) for k, v in kw.items()}
+    for terms in (22, 2):
+        assert N.gemm_plan(M, Nn, K, terms, batch=G, prologue=pro)["kernel"] == kernel
+        Wp = N.gemm_split_pack(W, terms=terms)
+        got = N.gemm_split(A, Wp, groups=1, pipe=None, **kw)
+        want = N.gemm_split(A, Wp, groups=1, pipe=0, **kw)
+        assert torch.equal(got, want), (terms, (got - want).abs().max().item())
+
+
 def test_kernel_choice_is_per_call_and_reentrant_across_streams(N):
     """The library keeps no switch: two streams that interleave calls on the same operands with DIFFERENT K-loop kernels
     (pipe=0 / pipe=1 at smoke's ragged 300 x 96 by 200 x 96 product, fp16 x 2 with per-row scales; pipe=3 / pipe=0 at a
