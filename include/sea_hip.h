@@ -783,6 +783,26 @@ int sea_train_ce_up_bwd(const float* low, const int64_t* y, const float* wgt, in
                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * T2u-ac: sea_train_ce_up_tile / _workspace_bytes / _fwd / _bwd with the interpolation of
+ * F.interpolate(low, (H, W), mode="bilinear", align_corners=True), PSPNet's final up-sampling (ddcat_psp.py:467, 474).
+ * Per axis: scale = (n_in - 1) / (n_out - 1) in float (0 for n_out == 1), src = scale * dst, i0 = (int)src,
+ * i1 = i0 + (i0 < n_in - 1), lam = src - i0; the four values are combined with the fused multiply-adds of
+ * sea_psp_upsample_ac (bitwise the tensor P2 would write).  Arguments, labels, words, loss plane, workspace layout,
+ * ownership, summation order and reproducibility are those of the align_corners = 0 entry points above, and
+ * sea_train_ohem_select runs unchanged after sea_train_ce_up_ac_fwd with reduce_mean = 0.  No plan (tile and
+ * workspace_bytes 0, fwd / bwd the argument error): C outside 2..192, H < h or W < w, or no tile edge whose region fits
+ * 72 pixels per axis and 64 KB of LDS (a ratio (n_out - 1) / (n_in - 1) above 34; n_in == 1, where the region is the
+ * whole axis, with n_out above about 60); the caller then runs sea_psp_upsample_ac and T2. */
+int sea_train_ce_up_ac_tile(int C, int h, int w, int H, int W);
+size_t sea_train_ce_up_ac_workspace_bytes(int B, int C, int h, int w, int H, int W);
+int sea_train_ce_up_ac_fwd(const float* low, const int64_t* y, const float* wgt, int64_t ignore_label, float thresh,
+                           int reduce_mean, int B, int C, int h, int w, int H, int W, float* loss_px, void* workspace,
+                           size_t workspace_bytes, void* words, void* stream);
+int sea_train_ce_up_ac_bwd(const float* low, const int64_t* y, const float* wgt, int64_t ignore_label, int ohem, int B,
+                           int C, int h, int w, int H, int W, const float* loss_px, const float* g, const void* words,
+                           float* dlow, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * T2u for power-of-two ratios (csrc/train_loss_up_pow2.hip): nn.CrossEntropyLoss(weight, ignore_index, reduction="mean")
  * on F.interpolate(low, (H, W), mode="bilinear", align_corners=False), loss AND un-normalised gradient in ONE pass.
  * Replaces, per prediction, uperforseg.py:416-434 (main head x4, auxiliary head x16) and segmenter.py:228 +

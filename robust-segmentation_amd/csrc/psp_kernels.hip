@@ -26,6 +26,7 @@
 //
 // P3  residual add + ReLU of a bottleneck (resnet_ddcat.py:102-105): y = max(a + r, 0); backward g' = y > 0 ? g : 0,
 //     the gradient of both a and r.  float4 per lane, grid-stride.
+#include "bilinear_map.h"
 #include "sea_common.h"
 
 namespace sea {
@@ -81,34 +82,7 @@ static void p1_grid(int rows, int rowlen, dim3& grid) {
 }
 
 // ---- P2 ------------------------------------------------------------------------------------------------------------
-__host__ __device__ __forceinline__ float psp_ac_scale(int n_in, int n_out) {
-  return n_out > 1 ? (float)(n_in - 1) / (float)(n_out - 1) : 0.f;
-}
-
-struct AcMap {
-  int i0, p;           // taps i0 and i0 + p
-  float l0, l1;
-};
-
-__device__ __forceinline__ AcMap ac_map(int dst, float scale, int n_in) {
-  const float src = scale * (float)dst;
-  AcMap a;
-  a.i0 = (int)src;
-  a.p = (a.i0 < n_in - 1) ? 1 : 0;
-  a.l1 = src - (float)a.i0;
-  a.l0 = 1.f - a.l1;
-  return a;
-}
-
-// l0y*(l0x*v00 + l1x*v01) + l1y*(l0x*v10 + l1x*v11) rounded exactly as ATen's compiled kernel rounds it (measured on
-// MI355X against F.interpolate: each sum's FIRST product is fused, the second rounded on its own); written with explicit
-// fmaf so that the result does not depend on how this translation unit's contraction happens to pair the terms
-__device__ __forceinline__ float lerp_ac(float v00, float v01, float v10, float v11, const AcMap& mx, const AcMap& my) {
-  const float t0 = fmaf(mx.l0, v00, mx.l1 * v01);
-  const float t1 = fmaf(mx.l0, v10, mx.l1 * v11);
-  return fmaf(my.l0, t0, my.l1 * t1);
-}
-
+// psp_ac_scale, ac_map and lerp_ac: bilinear_map.h (T2u-ac interpolates with the same definitions)
 // weight of input index i in output index o (0 if o does not read i)
 __device__ __forceinline__ float ac_weight(int o, int i, float scale, int n_in) {
   const AcMap a = ac_map(o, scale, n_in);

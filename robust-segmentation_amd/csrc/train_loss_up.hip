@@ -25,6 +25,13 @@
 // LDS: 4*(C*(TL+2)^2 + 6*RMAX + 2*(TL+3)) bytes in both kernels plus 16*RMAX^2 (four statistics planes of the region) in
 // the backward, RMAX = (TL+1)*ratio + 4.  TL is the largest edge <= 8 that keeps the backward within 64 KB (two
 // workgroups per CU) and RMAX within 72: x4 gives TL = 8 up to C = 95 and TL = 6 at C = 151 (55 KB); x16 gives TL = 2.
+//
+// T2u-ac: PSPNet up-samples its two heads with align_corners=True (P2, psp_kernels.hip).  The kernels are templates on the
+// interpolation rule (MapHalfPixel / MapCorners below): the axis map, its inverse, the expression tree of the four-tap
+// sum and the plan's region bound are the rule's, everything else (ownership, LDS layout, summation order, records,
+// workspace) is shared source.  The align_corners=False instantiation is the code it was before the template.  With
+// align_corners=True, src = scale * dst with scale = (h-1)/(H-1): x8 (PSPNet's 60 -> 473) gives TL = 6 at C = 21 (RMAX 60, 63 KB) and
+// TL = 4 at C = 151.
 #include "bilinear_map.h"
 #include "train_loss_common.h"
 
@@ -40,6 +47,46 @@ __device__ __forceinline__ float lerp2(float v00, float v01, float v10, float v1
   const float bot = (1.f - lx) * v10 + lx * v11;
   return (1.f - ly) * top + ly * bot;
 }
+
+// The two interpolation rules the kernels are instantiated for.  map: source pair and weight of a destination index;
+// first_ge: its inverse (first destination index whose i0 is >= t); lerp: the rule's expression tree; scale: the float
+// the launcher passes as rh / rw.
+struct MapHalfPixel {  // align_corners=False: ATen's area_pixel_compute_scale, axis_map_u, lerp2
+  static float scale(int n_in, int n_out) { return (float)n_in / (float)n_out; }
+  // TL + 1 source cells of at most ceil(ratio) pixels each, plus slack for the clamped border cells
+  static double region(int TL, int n_in, int n_out) { return (TL + 1) * ((double)n_out / n_in) + 4.0; }
+  __device__ static __forceinline__ AxisMapU map(int dst, float r, int n_in) { return axis_map_u(dst, r, n_in); }
+  __device__ static __forceinline__ int first_ge(int t, float r, int n_in, int n_out) {
+    return first_dst_ge(t, r, n_in, n_out);
+  }
+  __device__ static __forceinline__ float lerp(float v00, float v01, float v10, float v11, float lx, float ly) {
+    return lerp2(v00, v01, v10, v11, lx, ly);
+  }
+};
+
+struct MapCorners {  // align_corners=True: P2's psp_ac_scale, ac_map, lerp_ac (l0 = 1 - l1, as ac_map computes it)
+  static float scale(int n_in, int n_out) { return psp_ac_scale(n_in, n_out); }
+  // src = scale * dst: the TL + 1 cells cover (TL + 1) / scale pixels (+ 1 for the ends, + float rounding); with one
+  // source pixel the scale is 0 and every destination index reads it: the region is the whole axis
+  static double region(int TL, int n_in, int n_out) {
+    return n_in > 1 ? (TL + 1) * ((double)(n_out - 1) / (n_in - 1)) + 4.0 : (double)n_out;
+  }
+  __device__ static __forceinline__ AxisMapU map(int dst, float r, int n_in) {
+    const AcMap a = ac_map(dst, r, n_in);
+    AxisMapU m;
+    m.i0 = a.i0;
+    m.i1 = a.i0 + a.p;
+    m.lam = a.l1;
+    return m;
+  }
+  __device__ static __forceinline__ int first_ge(int t, float r, int n_in, int n_out) {
+    return first_dst_ge_ac(t, r, n_in, n_out);
+  }
+  __device__ static __forceinline__ float lerp(float v00, float v01, float v10, float v11, float lx, float ly) {
+    const AcMap mx = {0, 0, 1.f - lx, lx}, my = {0, 0, 1.f - ly, ly};
+    return lerp_ac(v00, v01, v10, v11, mx, my);
+  }
+};
 
 struct UpTile {
   int ya, xa, yb, xb;        // owned low-resolution tile [ya, yb) x [xa, xb)
@@ -74,6 +121,7 @@ __device__ __forceinline__ UpSmem up_carve(float* smem, int C, int TL, int RMAX)
 
 // phase 0 of both kernels: the low-resolution tile with its halo (clamped into the image) and the axis tables.
 // Ends with a barrier.
+template <class M>
 __device__ __forceinline__ UpTile up_stage(const UpSmem& s, const float* __restrict__ lowb, int C, int h, int wl, int H,
                                            int W, float rh, float rw, int TL, int RMAX) {
   const int TLP = TL + 2;
@@ -82,14 +130,14 @@ __device__ __forceinline__ UpTile up_stage(const UpSmem& s, const float* __restr
   t.xa = blockIdx.x * TL;
   t.yb = min(t.ya + TL, h);
   t.xb = min(t.xa + TL, wl);
-  t.Y0e = first_dst_ge(t.ya - 1, rh, h, H);
-  t.Y0o = first_dst_ge(t.ya, rh, h, H);
-  t.Y1 = first_dst_ge(t.yb, rh, h, H);
-  t.X0e = first_dst_ge(t.xa - 1, rw, wl, W);
-  t.X0o = first_dst_ge(t.xa, rw, wl, W);
-  t.X1 = first_dst_ge(t.xb, rw, wl, W);
-  // RMAX bounds the region by construction of the plan ((TL+1) source cells of at most ceil(ratio) pixels each); the
-  // clamp keeps every LDS index inside its table whatever the rounding of the float maps does
+  t.Y0e = M::first_ge(t.ya - 1, rh, h, H);
+  t.Y0o = M::first_ge(t.ya, rh, h, H);
+  t.Y1 = M::first_ge(t.yb, rh, h, H);
+  t.X0e = M::first_ge(t.xa - 1, rw, wl, W);
+  t.X0o = M::first_ge(t.xa, rw, wl, W);
+  t.X1 = M::first_ge(t.xb, rw, wl, W);
+  // RMAX bounds the region by construction of the plan (M::region: the pixels TL + 1 source cells can cover under this
+  // rule); the clamp keeps every LDS index inside its table whatever the rounding of the float maps does
   if (t.Y1 - t.Y0e > RMAX) t.Y0e = t.Y1 - RMAX;
   if (t.X1 - t.X0e > RMAX) t.X0e = t.X1 - RMAX;
   t.Y0o = max(t.Y0o, t.Y0e);
@@ -105,21 +153,21 @@ __device__ __forceinline__ UpTile up_stage(const UpSmem& s, const float* __restr
     s.lowt[i] = lowb[((int64_t)c * h + gy) * wl + gx];
   }
   for (int i = threadIdx.x; i < t.RH; i += 256) {
-    const AxisMapU m = axis_map_u(t.Y0e + i, rh, h);
+    const AxisMapU m = M::map(t.Y0e + i, rh, h);
     s.r_i0[i] = min(max(m.i0 - (t.ya - 1), 0), TLP - 1);
     s.r_i1[i] = min(max(m.i1 - (t.ya - 1), 0), TLP - 1);
     s.r_lam[i] = m.lam;
   }
   for (int i = threadIdx.x; i < t.RW; i += 256) {
-    const AxisMapU m = axis_map_u(t.X0e + i, rw, wl);
+    const AxisMapU m = M::map(t.X0e + i, rw, wl);
     s.c_i0[i] = min(max(m.i0 - (t.xa - 1), 0), TLP - 1);
     s.c_i1[i] = min(max(m.i1 - (t.xa - 1), 0), TLP - 1);
     s.c_lam[i] = m.lam;
   }
   if (threadIdx.x < TL + 3) {
     const int k = threadIdx.x;  // local cell index: global source index ya-1+k
-    s.rbeg[k] = min(max(first_dst_ge(t.ya - 1 + k, rh, h, H), t.Y0e), t.Y1) - t.Y0e;
-    s.cbeg[k] = min(max(first_dst_ge(t.xa - 1 + k, rw, wl, W), t.X0e), t.X1) - t.X0e;
+    s.rbeg[k] = min(max(M::first_ge(t.ya - 1 + k, rh, h, H), t.Y0e), t.Y1) - t.Y0e;
+    s.cbeg[k] = min(max(M::first_ge(t.xa - 1 + k, rw, wl, W), t.X0e), t.X1) - t.X0e;
   }
   __syncthreads();
   return t;
@@ -128,19 +176,20 @@ __device__ __forceinline__ UpTile up_stage(const UpSmem& s, const float* __restr
 // soft-max statistics of one full-resolution pixel, interpolated out of the tile: me = max_c z (-3e38 in place of -inf),
 // s = sum_c exp(z - me) in double, zy = z[lab] (0 if none).  Two passes over the classes: the maximum first, so that the
 // sum needs no rescaling.
+template <class M>
 __device__ __forceinline__ void up_px_stats(const float* __restrict__ lowt, int P2, int C, int o00, int o01, int o10,
                                             int o11, float lx, float ly, int lab, float& me, double& s, float& zy) {
   float m = -INFINITY;
   for (int c = 0; c < C; ++c) {
     const float* t = lowt + c * P2;
-    m = fmaxf(m, lerp2(t[o00], t[o01], t[o10], t[o11], lx, ly));
+    m = fmaxf(m, M::lerp(t[o00], t[o01], t[o10], t[o11], lx, ly));
   }
   me = (m == -INFINITY) ? -3.0e38f : m;
   s = 0.0;
   zy = 0.f;
   for (int c = 0; c < C; ++c) {
     const float* t = lowt + c * P2;
-    const float z = lerp2(t[o00], t[o01], t[o10], t[o11], lx, ly);
+    const float z = M::lerp(t[o00], t[o01], t[o10], t[o11], lx, ly);
     s += (double)expf(z - me);
     zy = (lab == c) ? z : zy;
   }
@@ -148,6 +197,7 @@ __device__ __forceinline__ void up_px_stats(const float* __restrict__ lowt, int 
 
 // ---- forward --------------------------------------------------------------------------------------------------------
 // grid = (tiles_x, tiles_y, B), block = 256.  One record per block, image-major.
+template <class M>
 __global__ __launch_bounds__(256) void train_ce_up_fwd_k(const float* __restrict__ low, const long long* __restrict__ y,
                                                          const float* __restrict__ w, long long ignore, float thresh,
                                                          int C, int h, int wl, int H, int W, float rh, float rw, int TL,
@@ -156,7 +206,7 @@ __global__ __launch_bounds__(256) void train_ce_up_fwd_k(const float* __restrict
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const UpSmem s = up_carve(smem, C, TL, RMAX);
   const int b = blockIdx.z, TLP = TL + 2, P2 = TLP * TLP;
-  const UpTile t = up_stage(s, low + (int64_t)b * C * h * wl, C, h, wl, H, W, rh, rw, TL, RMAX);
+  const UpTile t = up_stage<M>(s, low + (int64_t)b * C * h * wl, C, h, wl, H, W, rh, rw, TL, RMAX);
   const int ro = t.Y0o - t.Y0e, co = t.X0o - t.X0e;  // the owned part of the region starts here
   const int OH = t.Y1 - t.Y0o, OW = t.X1 - t.X0o;
   double lsum = 0.0, wsum = 0.0, hsum = 0.0;
@@ -174,7 +224,7 @@ __global__ __launch_bounds__(256) void train_ce_up_fwd_k(const float* __restrict
       const int r0 = s.r_i0[ri] * TLP, r1 = s.r_i1[ri] * TLP, c0 = s.c_i0[ci], c1 = s.c_i1[ci];
       float me, zy;
       double se;
-      up_px_stats(s.lowt, P2, C, r0 + c0, r0 + c1, r1 + c0, r1 + c1, s.c_lam[ci], s.r_lam[ri], lab, me, se, zy);
+      up_px_stats<M>(s.lowt, P2, C, r0 + c0, r0 + c1, r1 + c0, r1 + c1, s.c_lam[ci], s.r_lam[ri], lab, me, se, zy);
       // -log_softmax(z)[y] = log(sum exp(z - m)) - (z_y - m), rounded to float once (T2)
       const float ce = (float)(log(se) - ((double)zy - (double)me));
       const float wy = (w != nullptr) ? w[lab] : 1.f;
@@ -219,7 +269,7 @@ __global__ __launch_bounds__(256) void train_ce_up_fwd_k(const float* __restrict
 //   (bilinear weight) * K * (softmax(z)_c - [c == y]),  K = g * coef * w[y].
 // CK classes per thread in phase B: 8 amortises the per-pixel statistics reads; 1 where a tile has too few
 // (pixel, chunk) items to occupy the block (large ratios: TL = 2).
-template <int CK>
+template <class M, int CK>
 __global__ __launch_bounds__(256) void train_ce_up_bwd_k(const float* __restrict__ low, const long long* __restrict__ y,
                                                          const float* __restrict__ w, long long ignore, int ohem, int C,
                                                          int h, int wl, int H, int W, float rh, float rw, int TL,
@@ -234,7 +284,7 @@ __global__ __launch_bounds__(256) void train_ce_up_bwd_k(const float* __restrict
   float* pK = pA + RMAX * RMAX;
   int* plab = (int*)(pK + RMAX * RMAX);
   const int b = blockIdx.z, TLP = TL + 2, P2 = TLP * TLP;
-  const UpTile t = up_stage(s, low + (int64_t)b * C * h * wl, C, h, wl, H, W, rh, rw, TL, RMAX);
+  const UpTile t = up_stage<M>(s, low + (int64_t)b * C * h * wl, C, h, wl, H, W, rh, rw, TL, RMAX);
   const float gc = g[0] * words->coef;
 
   // ---- phase A: statistics of every selected pixel of the extended region
@@ -250,7 +300,7 @@ __global__ __launch_bounds__(256) void train_ce_up_bwd_k(const float* __restrict
       const int r0 = s.r_i0[ri] * TLP, r1 = s.r_i1[ri] * TLP, c0 = s.c_i0[ci], c1 = s.c_i1[ci];
       float zy;
       double se;
-      up_px_stats(s.lowt, P2, C, r0 + c0, r0 + c1, r1 + c0, r1 + c1, s.c_lam[ci], s.r_lam[ri], lab, me, se, zy);
+      up_px_stats<M>(s.lowt, P2, C, r0 + c0, r0 + c1, r1 + c0, r1 + c1, s.c_lam[ci], s.r_lam[ri], lab, me, se, zy);
       K = gc * ((w != nullptr) ? w[lab] : 1.f);
       A = (float)((double)K / se);
     }
@@ -307,7 +357,7 @@ __global__ __launch_bounds__(256) void train_ce_up_bwd_k(const float* __restrict
             const float mm = pm[p], A = pA[p], K = pK[p];
 #pragma unroll
             for (int k = 0; k < CK; ++k) {
-              const float e = expf(lerp2(v00[k], v01[k], v10[k], v11[k], lx, ly) - mm);
+              const float e = expf(M::lerp(v00[k], v01[k], v10[k], v11[k], lx, ly) - mm);
               const float tv = A * e;
               const float dz = (lb == c0 + k) ? tv - K : tv;  // T2's per-pixel gradient, rounded as T2 rounds it
               acc[k] += (double)wv * (double)dz;
@@ -327,13 +377,14 @@ struct UpTrainPlan {
   size_t lds_fwd, lds_bwd;
 };
 
-// the low-resolution tile edge: as large as the LDS budget of the backward and the region bound allow
+// the low-resolution tile edge: as large as the LDS budget of the backward and the region bound allow.  M::region bounds
+// the full-resolution rows (columns) whose i0 falls into TL + 1 consecutive source cells.
+template <class M>
 static bool plan_train_up(int C, int h, int wl, int H, int W, UpTrainPlan* out) {
   if (C < kUpMinClasses || C > kUpMaxClasses || h <= 0 || wl <= 0 || H < h || W < wl) return false;
-  const double sh = (double)H / h, sw = (double)W / wl;
-  const double sc = sh > sw ? sh : sw;
   for (int TL = 8; TL >= 1; --TL) {
-    const double rmax_d = (TL + 1) * sc + 4.0;
+    const double rh_d = M::region(TL, h, H), rw_d = M::region(TL, wl, W);
+    const double rmax_d = rh_d > rw_d ? rh_d : rw_d;
     if (rmax_d > (double)kUpMaxRegion) continue;
     const int RMAX = (int)rmax_d;
     const size_t TLP = TL + 2;
@@ -354,34 +405,27 @@ static bool plan_train_up(int C, int h, int wl, int H, int W, UpTrainPlan* out) 
 
 static inline bool up_aligned(const void* p, size_t bytes) { return (((uintptr_t)p) % bytes) == 0; }
 
-}  // namespace sea
-
-using namespace sea;
-
-extern "C" int sea_train_ce_up_tile(int C, int h, int w, int H, int W) {
+template <class M>
+static size_t up_workspace_bytes(int B, int C, int h, int w, int H, int W) {
   UpTrainPlan p;
-  return plan_train_up(C, h, w, H, W, &p) ? p.TL : 0;
-}
-
-extern "C" size_t sea_train_ce_up_workspace_bytes(int B, int C, int h, int w, int H, int W) {
-  UpTrainPlan p;
-  if (B <= 0 || !plan_train_up(C, h, w, H, W, &p)) return 0;
+  if (B <= 0 || !plan_train_up<M>(C, h, w, H, W, &p)) return 0;
   return kOffRecords + (size_t)B * p.tiles_x * p.tiles_y * sizeof(TrainRecord);
 }
 
-extern "C" int sea_train_ce_up_fwd(const float* low, const int64_t* y, const float* wgt, int64_t ignore_label,
-                                   float thresh, int reduce_mean, int B, int C, int h, int w, int H, int W,
-                                   float* loss_px, void* workspace, size_t workspace_bytes, void* words, void* stream) {
+template <class M>
+static int up_fwd(const float* low, const int64_t* y, const float* wgt, int64_t ignore_label, float thresh,
+                  int reduce_mean, int B, int C, int h, int w, int H, int W, float* loss_px, void* workspace,
+                  size_t workspace_bytes, void* words, void* stream) {
   SEA_CHECK_ARG(low && y && loss_px && workspace && words);
   UpTrainPlan p;
-  SEA_CHECK_ARG(B > 0 && B <= 65535 && plan_train_up(C, h, w, H, W, &p));
+  SEA_CHECK_ARG(B > 0 && B <= 65535 && plan_train_up<M>(C, h, w, H, W, &p));
   SEA_CHECK_ARG((int64_t)B * H * W < ((int64_t)1 << 31));
-  SEA_CHECK_ARG(workspace_bytes >= sea_train_ce_up_workspace_bytes(B, C, h, w, H, W));
+  SEA_CHECK_ARG(workspace_bytes >= up_workspace_bytes<M>(B, C, h, w, H, W));
   SEA_CHECK_ARG(up_aligned(workspace, 16) && up_aligned(words, 8) && up_aligned(y, 8) && up_aligned(low, 4));
   TrainRecord* rec = (TrainRecord*)((char*)workspace + kOffRecords);
   hipStream_t s = (hipStream_t)stream;
-  const float rh = (float)h / (float)H, rw = (float)w / (float)W;  // ATen: area_pixel_compute_scale
-  auto k = train_ce_up_fwd_k;
+  const float rh = M::scale(h, H), rw = M::scale(w, W);
+  auto k = train_ce_up_fwd_k<M>;
   if (p.lds_fwd > 48 * 1024)
     (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_fwd);
   hipLaunchKernelGGL(k, dim3(p.tiles_x, p.tiles_y, B), dim3(256), p.lds_fwd, s, low, (const long long*)y, wgt,
@@ -392,23 +436,21 @@ extern "C" int sea_train_ce_up_fwd(const float* low, const int64_t* y, const flo
   SEA_RETURN_LAST();
 }
 
-extern "C" int sea_train_ce_up_bwd(const float* low, const int64_t* y, const float* wgt, int64_t ignore_label, int ohem,
-                                   int B, int C, int h, int w, int H, int W, const float* loss_px, const float* g,
-                                   const void* words, float* dlow, void* workspace, size_t workspace_bytes,
-                                   void* stream) {
-  (void)workspace;  // the gather needs no scratch: the arguments are kept for a variant with partial sums
-  (void)workspace_bytes;
+template <class M>
+static int up_bwd(const float* low, const int64_t* y, const float* wgt, int64_t ignore_label, int ohem, int B, int C,
+                  int h, int w, int H, int W, const float* loss_px, const float* g, const void* words, float* dlow,
+                  void* stream) {
   SEA_CHECK_ARG(low && y && loss_px && g && words && dlow);
   UpTrainPlan p;
-  SEA_CHECK_ARG(B > 0 && B <= 65535 && plan_train_up(C, h, w, H, W, &p));
+  SEA_CHECK_ARG(B > 0 && B <= 65535 && plan_train_up<M>(C, h, w, H, W, &p));
   SEA_CHECK_ARG((int64_t)B * H * W < ((int64_t)1 << 31));
   SEA_CHECK_ARG(up_aligned(words, 8) && up_aligned(y, 8) && up_aligned(low, 4) && up_aligned(dlow, 4));
   hipStream_t s = (hipStream_t)stream;
-  const float rh = (float)h / (float)H, rw = (float)w / (float)W;
+  const float rh = M::scale(h, H), rw = M::scale(w, W);
   const dim3 grid(p.tiles_x, p.tiles_y, B), block(256);
 #define SEA_T2U_BWD(CK)                                                                                              \
   do {                                                                                                               \
-    auto k = train_ce_up_bwd_k<CK>;                                                                                  \
+    auto k = train_ce_up_bwd_k<M, CK>;                                                                               \
     if (p.lds_bwd > 48 * 1024)                                                                                       \
       (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bwd);         \
     hipLaunchKernelGGL(k, grid, block, p.lds_bwd, s, low, (const long long*)y, wgt, (long long)ignore_label, ohem, C, \
@@ -420,4 +462,61 @@ extern "C" int sea_train_ce_up_bwd(const float* low, const int64_t* y, const flo
     SEA_T2U_BWD(1);
 #undef SEA_T2U_BWD
   SEA_RETURN_LAST();
+}
+
+}  // namespace sea
+
+using namespace sea;
+
+extern "C" int sea_train_ce_up_tile(int C, int h, int w, int H, int W) {
+  UpTrainPlan p;
+  return plan_train_up<MapHalfPixel>(C, h, w, H, W, &p) ? p.TL : 0;
+}
+
+extern "C" size_t sea_train_ce_up_workspace_bytes(int B, int C, int h, int w, int H, int W) {
+  return up_workspace_bytes<MapHalfPixel>(B, C, h, w, H, W);
+}
+
+extern "C" int sea_train_ce_up_fwd(const float* low, const int64_t* y, const float* wgt, int64_t ignore_label,
+                                   float thresh, int reduce_mean, int B, int C, int h, int w, int H, int W,
+                                   float* loss_px, void* workspace, size_t workspace_bytes, void* words, void* stream) {
+  return up_fwd<MapHalfPixel>(low, y, wgt, ignore_label, thresh, reduce_mean, B, C, h, w, H, W, loss_px, workspace,
+                              workspace_bytes, words, stream);
+}
+
+// workspace: the gather needs no scratch; the arguments are kept for a variant with partial sums
+extern "C" int sea_train_ce_up_bwd(const float* low, const int64_t* y, const float* wgt, int64_t ignore_label, int ohem,
+                                   int B, int C, int h, int w, int H, int W, const float* loss_px, const float* g,
+                                   const void* words, float* dlow, void* workspace, size_t workspace_bytes,
+                                   void* stream) {
+  (void)workspace;
+  (void)workspace_bytes;
+  return up_bwd<MapHalfPixel>(low, y, wgt, ignore_label, ohem, B, C, h, w, H, W, loss_px, g, words, dlow, stream);
+}
+
+// ---- T2u-ac: the same kernels with PSPNet's align_corners=True rule ----------------------------------------------------
+extern "C" int sea_train_ce_up_ac_tile(int C, int h, int w, int H, int W) {
+  UpTrainPlan p;
+  return plan_train_up<MapCorners>(C, h, w, H, W, &p) ? p.TL : 0;
+}
+
+extern "C" size_t sea_train_ce_up_ac_workspace_bytes(int B, int C, int h, int w, int H, int W) {
+  return up_workspace_bytes<MapCorners>(B, C, h, w, H, W);
+}
+
+extern "C" int sea_train_ce_up_ac_fwd(const float* low, const int64_t* y, const float* wgt, int64_t ignore_label,
+                                      float thresh, int reduce_mean, int B, int C, int h, int w, int H, int W,
+                                      float* loss_px, void* workspace, size_t workspace_bytes, void* words,
+                                      void* stream) {
+  return up_fwd<MapCorners>(low, y, wgt, ignore_label, thresh, reduce_mean, B, C, h, w, H, W, loss_px, workspace,
+                            workspace_bytes, words, stream);
+}
+
+extern "C" int sea_train_ce_up_ac_bwd(const float* low, const int64_t* y, const float* wgt, int64_t ignore_label,
+                                      int ohem, int B, int C, int h, int w, int H, int W, const float* loss_px,
+                                      const float* g, const void* words, float* dlow, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  (void)workspace;
+  (void)workspace_bytes;
+  return up_bwd<MapCorners>(low, y, wgt, ignore_label, ohem, B, C, h, w, H, W, loss_px, g, words, dlow, stream);
 }

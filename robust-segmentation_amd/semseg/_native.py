@@ -133,6 +133,10 @@ _SIGS = {
     "sea_train_ce_up_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "sea_train_ce_up_fwd": (_i, [_vp, _vp, _vp, _i64, _f, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _vp]),
     "sea_train_ce_up_bwd": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sea_train_ce_up_ac_tile": (_i, [_i, _i, _i, _i, _i]),
+    "sea_train_ce_up_ac_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "sea_train_ce_up_ac_fwd": (_i, [_vp, _vp, _vp, _i64, _f, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _vp]),
+    "sea_train_ce_up_ac_bwd": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sea_train_ce_up_pow2_supported": (_i, [_i, _i, _i, _i, _i]),
     "sea_train_ce_up_pow2_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "sea_train_ce_up_pow2_fwd": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _vp]),
@@ -462,40 +466,53 @@ def _train_up_args(low, size, y, weight):
     return B, Cc, h, w, H, W, weight
 
 
-def train_ce_up_supported(low, size) -> bool:
+def _up_entry(name: str, align_corners: bool):
+    """the T2u entry point ``name`` (tile, workspace_bytes, fwd, bwd) for the interpolation rule"""
+    L = lib()
+    if align_corners:        # T2u-ac
+        return {"tile": L.sea_train_ce_up_ac_tile, "workspace_bytes": L.sea_train_ce_up_ac_workspace_bytes,
+                "fwd": L.sea_train_ce_up_ac_fwd, "bwd": L.sea_train_ce_up_ac_bwd}[name]
+    return {"tile": L.sea_train_ce_up_tile, "workspace_bytes": L.sea_train_ce_up_workspace_bytes,
+            "fwd": L.sea_train_ce_up_fwd, "bwd": L.sea_train_ce_up_bwd}[name]
+
+
+def train_ce_up_supported(low, size, align_corners: bool = False) -> bool:
     """Whether T2u has a kernel for this shape (class count 2..192, a tiling for the ratio); the caller takes
-    ``F.interpolate`` + T2 otherwise."""
+    ``F.interpolate`` + T2 otherwise.  ``align_corners``: the interpolation rule, here and below (True: T2u-ac)."""
     B, Cc, h, w = low.shape
-    return lib().sea_train_ce_up_workspace_bytes(B, Cc, h, w, int(size[0]), int(size[1])) != 0
+    return _up_entry("workspace_bytes", align_corners)(B, Cc, h, w, int(size[0]), int(size[1])) != 0
 
 
-def train_ce_up_tile(C: int, h: int, w: int, H: int, W: int) -> int:
+def train_ce_up_tile(C: int, h: int, w: int, H: int, W: int, align_corners: bool = False) -> int:
     """Edge of the low-resolution tile one workgroup owns for this shape (0: no T2u kernel)."""
-    return int(lib().sea_train_ce_up_tile(C, h, w, H, W))
+    return int(_up_entry("tile", align_corners)(C, h, w, H, W))
 
 
-def train_ce_up_forward(low, size, y, weight, ignore_label: int, thresh: float = 0.0, ohem: bool = False):
+def train_ce_up_forward(low, size, y, weight, ignore_label: int, thresh: float = 0.0, ohem: bool = False,
+                        align_corners: bool = False):
     """T2u forward (+ the OHEM select, T2's, on the full-resolution loss plane) on LOW-resolution logits (B,C,h,w);
     ``size`` = (H, W) of the labels.  Returns (loss, loss_px, words) as ``train_ce_forward``.  Nothing is read by the host."""
     B, Cc, h, w, H, W, weight = _train_up_args(low, size, y, weight)
     dev = low.device
     L = lib()
-    nb = L.sea_train_ce_up_workspace_bytes(B, Cc, h, w, H, W)
+    nb = _up_entry("workspace_bytes", align_corners)(B, Cc, h, w, H, W)
     if nb == 0:
-        raise SeaNativeError(f"no T2u kernel for C = {Cc}, {(h, w)} -> {(H, W)}")
+        raise SeaNativeError(f"no T2u kernel for C = {Cc}, {(h, w)} -> {(H, W)}"
+                             + (" with align_corners=True" if align_corners else ""))
     workspace = torch.empty(nb, dtype=torch.uint8, device=dev)
     words = torch.zeros(8, dtype=torch.float64, device=dev)
     loss_px = torch.empty(B, H * W, dtype=torch.float32, device=dev)
-    _check(L.sea_train_ce_up_fwd(_p(low), _p(y), _p(weight), int(ignore_label), float(thresh), 0 if ohem else 1, B, Cc,
-                                 h, w, H, W, _p(loss_px), _p(workspace), nb, _p(words), _stream()),
-           "sea_train_ce_up_fwd")
+    _check(_up_entry("fwd", align_corners)(_p(low), _p(y), _p(weight), int(ignore_label), float(thresh),
+                                           0 if ohem else 1, B, Cc, h, w, H, W, _p(loss_px), _p(workspace), nb, _p(words),
+                                           _stream()), "sea_train_ce_up_ac_fwd" if align_corners else "sea_train_ce_up_fwd")
     if ohem:
         _check(L.sea_train_ohem_select(_p(loss_px), B * H * W, _p(workspace), nb, _p(words), _stream()),
                "sea_train_ohem_select")
     return words.view(torch.float32)[TRAIN_WORDS_F32["loss"]].clone(), loss_px, words
 
 
-def train_ce_up_backward(low, size, y, weight, ignore_label: int, ohem: bool, loss_px, words, g):
+def train_ce_up_backward(low, size, y, weight, ignore_label: int, ohem: bool, loss_px, words, g,
+                         align_corners: bool = False):
     """T2u backward: d loss / d low (fp32, every element written).  ``g``: the upstream gradient, a 0-dim device tensor."""
     B, Cc, h, w, H, W, weight = _train_up_args(low, size, y, weight)
     _dev(loss_px, words, g)
@@ -503,9 +520,9 @@ def train_ce_up_backward(low, size, y, weight, ignore_label: int, ohem: bool, lo
         raise SeaNativeError("the upstream gradient of the criterion is a scalar")
     g = g.reshape(1).to(torch.float32)
     dlow = torch.empty_like(low)
-    _check(lib().sea_train_ce_up_bwd(_p(low), _p(y), _p(weight), int(ignore_label), 1 if ohem else 0, B, Cc, h, w, H, W,
-                                     _p(_f32c(loss_px)), _p(g), _p(words), _p(dlow), None, 0, _stream()),
-           "sea_train_ce_up_bwd")
+    _check(_up_entry("bwd", align_corners)(_p(low), _p(y), _p(weight), int(ignore_label), 1 if ohem else 0, B, Cc, h, w,
+                                           H, W, _p(_f32c(loss_px)), _p(g), _p(words), _p(dlow), None, 0, _stream()),
+           "sea_train_ce_up_ac_bwd" if align_corners else "sea_train_ce_up_bwd")
     return dlow
 
 

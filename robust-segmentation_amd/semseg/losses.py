@@ -14,6 +14,10 @@ mode="bilinear", align_corners=False), labels)`` for the low-resolution output `
 (csrc/train_loss_up.hip), which interpolates inside the criterion's kernels: the full-resolution logits and their gradient are
 never created.  A class count T2u has no kernel for (outside 2..192) takes the composition with T2.
 
+``upsampled(preds_low, labels, align_corners=True)`` is the same for PSPNet's rule, ``F.interpolate(..., align_corners=True)``:
+``native=True`` runs T2u-ac (the kernels of csrc/train_loss_up.hip instantiated for that rule), or P2 (``upsample_ac``) + T2
+where T2u-ac has no plan; ``up_kernel="pow2"`` takes the gather there (the single-pass kernel is an align_corners=False kernel).
+
 ``up_kernel`` chooses T2u's kernel for ``upsampled``: ``"gather"`` (the default: csrc/train_loss_up.hip, any ratio, two
 launches) or ``"pow2"`` (csrc/train_loss_up_pow2.hip: forward and gradient in one pass for ``CrossEntropy`` on a prediction
 that is exactly 1/4 or 1/16 of the labels on both axes; any other prediction goes where ``"gather"`` sends it).
@@ -66,11 +70,12 @@ class _NativeCriterionUp(torch.autograd.Function):
     """T2u: as ``_NativeCriterion`` on low-resolution logits; the labels' size is the up-sampling target."""
 
     @staticmethod
-    def forward(ctx, low, labels, weight, ignore_label, thresh, ohem):
+    def forward(ctx, low, labels, weight, ignore_label, thresh, ohem, align_corners=False):
         from . import _native as N
-        loss, loss_px, words = N.train_ce_up_forward(low, labels.shape[-2:], labels, weight, ignore_label, thresh, ohem)
+        loss, loss_px, words = N.train_ce_up_forward(low, labels.shape[-2:], labels, weight, ignore_label, thresh, ohem,
+                                                     align_corners=align_corners)
         ctx.save_for_backward(low, labels, loss_px, words)
-        ctx.weight, ctx.ignore_label, ctx.ohem = weight, ignore_label, ohem
+        ctx.weight, ctx.ignore_label, ctx.ohem, ctx.align_corners = weight, ignore_label, ohem, align_corners
         ctx.mark_non_differentiable(words)
         return loss, words
 
@@ -79,7 +84,7 @@ class _NativeCriterionUp(torch.autograd.Function):
         from . import _native as N
         low, labels, loss_px, words = ctx.saved_tensors
         return (N.train_ce_up_backward(low, labels.shape[-2:], labels, ctx.weight, ctx.ignore_label, ctx.ohem, loss_px,
-                                       words, g), None, None, None, None, None)
+                                       words, g, align_corners=ctx.align_corners), None, None, None, None, None, None)
 
 
 class _NativeCriterionUpPow2(torch.autograd.Function):
@@ -109,8 +114,8 @@ def _check_up_kernel(up_kernel):
     return up_kernel
 
 
-def _upsample(p, labels):
-    return F.interpolate(p, size=labels.shape[-2:], mode="bilinear", align_corners=False)
+def _upsample(p, labels, align_corners=False):
+    return F.interpolate(p, size=labels.shape[-2:], mode="bilinear", align_corners=align_corners)
 
 
 class _AuxWeighted(nn.Module):
@@ -132,17 +137,26 @@ class _Upsampled(_AuxWeighted):
     def _thresh(self) -> float:
         return 0.0
 
-    def upsampled(self, preds_low, labels: Tensor) -> Tensor:
+    def upsampled(self, preds_low, labels: Tensor, align_corners: bool = False) -> Tensor:
+        align_corners = bool(align_corners)
         if isinstance(preds_low, tuple):
-            return sum(w * self._upsampled(p, labels) for p, w in zip(preds_low, self.aux_weights))
-        return self._upsampled(preds_low, labels)
+            return sum(w * self._upsampled(p, labels, align_corners) for p, w in zip(preds_low, self.aux_weights))
+        return self._upsampled(preds_low, labels, align_corners)
 
-    def _upsampled(self, low, labels):
+    def _upsampled(self, low, labels, align_corners=False):
         if self.native:
             from . import _native as N
             if not (low.is_cuda and labels.is_cuda):
                 raise N.SeaNativeError("native=True criteria work on HIP device tensors only (no CPU fallback)")
             w = self.criterion.weight
+            if align_corners:
+                if low.dim() == 4 and N.train_ce_up_supported(low, labels.shape[-2:], align_corners=True):
+                    loss, self.last_words = _NativeCriterionUp.apply(
+                        low.float().contiguous(), labels, None if w is None else w.detach().float(),
+                        self.criterion.ignore_index, self._thresh(), self._ohem, True)
+                    return loss
+                from .models.pspnet import _up_ac_train   # no T2u-ac kernel for this shape: P2 up-sampling + T2
+                return self._forward(_up_ac_train(low.float(), labels.shape[-2:]), labels)
             if (self.up_kernel == "pow2" and not self._ohem
                     and N.train_ce_up_pow2_supported(low, labels.shape[-2:])):
                 loss, self.last_words = _NativeCriterionUpPow2.apply(
@@ -156,7 +170,7 @@ class _Upsampled(_AuxWeighted):
                 return loss
             from .models.convnext_upernet import _up   # no T2u kernel for this shape: M2 up-sampling + T2
             return self._forward(_up(low, labels.shape[-2:]), labels)
-        return self._forward(_upsample(low, labels), labels)
+        return self._forward(_upsample(low, labels, align_corners), labels)
 
 
 class CrossEntropy(_Upsampled):

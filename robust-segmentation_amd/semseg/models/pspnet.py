@@ -22,7 +22,18 @@ return value ``(main_loss, aux_loss, x)``; every BatchNorm runs on T1 (train-mod
 the following ReLU / residual add + ReLU in HIP) after the library convolution, the dilated 3x3 convolutions become P1
 split -> dense 3x3 convolutions of the B*d*d sub-images -> P1 merge, and the align_corners=True up-samplings run on P2.
 
+``TRAIN_CRITERION`` (read once from ``SEA_PSP_TRAIN_CRITERION``; ``torch`` | ``native`` | ``fused``, default ``torch``)
+chooses the tail of that training forward when ``model.criterion`` is a plain mean ``nn.CrossEntropyLoss`` without label
+smoothing (any other criterion keeps the torch line; ``weight`` and ``ignore_index`` are honoured):
+- ``torch``: P2 on both heads, then ``model.criterion`` on the two full-resolution tensors;
+- ``native``: P2 on both heads, then T2 (csrc/train_loss.hip) in place of the library's cross-entropy;
+- ``fused``: T2u-ac (csrc/train_loss_up.hip, align_corners=True) on the heads' LOW-resolution logits: no full-resolution
+  tensor is created, and the third element of the return value is ``None`` (as UperNet's ``(loss, None)``).  With
+  ``zoom_factor == 1`` there is nothing to fuse and the mode is ``native``.
+
 ``USE_NATIVE = False`` runs the plain torch forward in both modes (A/B runs, the stock yardstick of the tests)."""
+import os
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -33,6 +44,10 @@ from .convnext_upernet import (_PointwiseRelu, _WinoConv3x3, _classify, _adaptiv
 
 USE_NATIVE = True
 _CL = torch.channels_last
+TRAIN_CRITERIA = ("torch", "native", "fused")
+TRAIN_CRITERION = os.environ.get("SEA_PSP_TRAIN_CRITERION", "").strip() or "torch"
+if TRAIN_CRITERION not in TRAIN_CRITERIA:
+    raise ValueError(f"SEA_PSP_TRAIN_CRITERION must be one of {TRAIN_CRITERIA}, got {TRAIN_CRITERION!r}")
 
 
 # ---------------------------------------------------------------------------------------------------- modules
@@ -478,9 +493,29 @@ def _native_train_forward(model, x, y, size):
         x = _UpCatAC.apply(tuple(x.shape[2:]), _dense_cl(x), *[_dense_cl(b) for b in branches])
     cls, aux = model.cls, model.aux
     x = cls[4](cls[3](_bn_train(cls[1], _conv_train(cls[0], x), True)))
+    a = aux[4](aux[3](_bn_train(aux[1], _conv_train(aux[0], x_tmp), True)))
+    crit = _device_criterion(model.criterion, y)
+    if crit is not None:
+        y = y.contiguous()
+    if crit is not None and TRAIN_CRITERION == "fused" and model.zoom_factor != 1:
+        assert tuple(y.shape[-2:]) == tuple(size)      # (F.cross_entropy would refuse any other label size)
+        return crit.upsampled(x, y, align_corners=True), crit.upsampled(a, y, align_corners=True), None
     if model.zoom_factor != 1:
         x = _up_ac_train(x, size)
-    a = aux[4](aux[3](_bn_train(aux[1], _conv_train(aux[0], x_tmp), True)))
-    if model.zoom_factor != 1:
         a = _up_ac_train(a, size)
+    if crit is not None:
+        return crit(x.contiguous(), y), crit(a.contiguous(), y), x
     return model.criterion(x, y), model.criterion(a, y), x
+
+
+def _device_criterion(criterion, y):
+    """``TRAIN_CRITERION`` native / fused: ``criterion`` as a ``semseg.losses.CrossEntropy(native=True)`` (T2 / T2u-ac) if it
+    is a plain mean cross-entropy over int64 device labels, else None (the torch line).  Built per call: it holds no state
+    but the criterion's own weight tensor."""
+    if TRAIN_CRITERION not in TRAIN_CRITERIA:
+        raise ValueError(f"pspnet.TRAIN_CRITERION must be one of {TRAIN_CRITERIA}, got {TRAIN_CRITERION!r}")
+    if (TRAIN_CRITERION == "torch" or type(criterion) is not nn.CrossEntropyLoss or criterion.reduction != "mean"
+            or criterion.label_smoothing != 0 or y is None or not y.is_cuda or y.dtype != torch.int64 or y.dim() != 3):
+        return None
+    from ..losses import CrossEntropy
+    return CrossEntropy(criterion.ignore_index, criterion.weight, native=True)

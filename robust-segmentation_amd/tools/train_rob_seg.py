@@ -27,6 +27,10 @@ parameter gradients, fused stochastic-depth tail; ``semseg.models.convnext_upern
 ``semseg.models.convnext_upernet.TRAIN_FUSED_CRITERION``), and the Segmenter branch's into its one (the model's masks at 1/16
 resolution through ``SegMenter.forward(im, lowres=True)``); ``--fused-kernel pow2`` runs them on the single-pass x4 / x16 kernel
 (``TRAIN_FUSED_KERNEL``).
+On the PSPNet branch ``--native-criterion`` computes the two cross-entropies of the training forward with T2 after the P2
+up-samplings, and ``--fused-criterion`` (which wins if both are given) with T2u-ac on the heads' low-resolution logits, for
+this run (``semseg.models.pspnet.TRAIN_CRITERION``); ``--fused-kernel`` has no effect there (the single-pass kernel is an
+align_corners=False kernel).
 """
 from __future__ import annotations
 
@@ -47,6 +51,7 @@ if _PKG not in sys.path:
 
 from semseg import attacker  # noqa: E402
 from semseg.models import convnext_upernet as _convnext  # noqa: E402
+from semseg.models import pspnet as _pspnet  # noqa: E402
 from semseg.models import PSPNet, UperNetForSemanticSegmentation, create_segmenter  # noqa: E402
 from semseg.val import Pgd_Attack, Pgd_Attack_1  # noqa: E402
 
@@ -171,14 +176,16 @@ def _main(argv=None):
                     help="save a sample of parameter tensors and of their (rank-averaged) gradients of the last step")
     ap.add_argument("--native-criterion", action="store_true",
                     help="Segmenter branch: compute the outer step's criterion with get_loss(cfg LOSS.NAME, -1, None, "
-                         "native=True) (T2, csrc/train_loss.hip) instead of F.cross_entropy")
+                         "native=True) (T2, csrc/train_loss.hip) instead of F.cross_entropy.  PSPNet branch: the two "
+                         "cross-entropies of the model's training forward on T2 (pspnet.TRAIN_CRITERION = native)")
     ap.add_argument("--native-blocks", action="store_true",
                     help="ConvNeXt trunk: train-mode blocks and trainable LayerNorms in NHWC on libsea_hip (T3, fp32; "
                          "csrc/ln_kernels.hip, csrc/block_tail.hip) for this run")
     ap.add_argument("--fused-criterion", action="store_true",
                     help="UperNet and Segmenter branches: the outer step's cross-entropies take the heads' low-resolution "
                          "logits (1/4 and 1/16; Segmenter's masks at 1/16) and interpolate inside the criterion (T2u, "
-                         "csrc/train_loss_up.hip) for this run; no full-resolution logits are created")
+                         "csrc/train_loss_up.hip) for this run; no full-resolution logits are created.  PSPNet branch: "
+                         "the same with align_corners=True on its two x8 heads (pspnet.TRAIN_CRITERION = fused)")
     ap.add_argument("--fused-kernel", choices=("gather", "pow2"), default="gather",
                     help="with --fused-criterion: T2u's kernel.  gather = any ratio, two launches; pow2 = forward and "
                          "gradient in one pass for x4 / x16 (csrc/train_loss_up_pow2.hip)")
@@ -188,6 +195,8 @@ def _main(argv=None):
     if args.fused_criterion:
         _convnext.TRAIN_FUSED_CRITERION = True
         _convnext.TRAIN_FUSED_KERNEL = args.fused_kernel
+    if args.fused_criterion or args.native_criterion:      # read by PSPNet's training forward only
+        _pspnet.TRAIN_CRITERION = "fused" if args.fused_criterion else "native"
     with open(args.cfg) as f:
         cfg = yaml.load(f, Loader=yaml.SafeLoader)
     train_cfg, model_cfg, data_cfg = cfg["TRAIN"], cfg["MODEL"], cfg["DATASET"]
@@ -321,6 +330,7 @@ def _main(argv=None):
         out["native_blocks"] = bool(_convnext.TRAIN_NATIVE_BLOCKS)
         out["fused_criterion"] = bool(_convnext.TRAIN_FUSED_CRITERION)
         out["fused_kernel"] = _convnext.TRAIN_FUSED_KERNEL if _convnext.TRAIN_FUSED_CRITERION else None
+        out["psp_criterion"] = _pspnet.TRAIN_CRITERION if psp else None
         print(json.dumps(out))
         if args.json:
             json.dump(out, open(args.json, "w"))
@@ -340,6 +350,7 @@ def main(argv=None):
     result record (the JSON line it prints)."""
     prev, prev_blocks = torch.backends.cudnn.benchmark, _convnext.TRAIN_NATIVE_BLOCKS
     prev_fused, prev_kernel = _convnext.TRAIN_FUSED_CRITERION, _convnext.TRAIN_FUSED_KERNEL
+    prev_psp = _pspnet.TRAIN_CRITERION
     try:
         return _main(argv)
     finally:
@@ -347,6 +358,7 @@ def main(argv=None):
         _convnext.TRAIN_NATIVE_BLOCKS = prev_blocks
         _convnext.TRAIN_FUSED_CRITERION = prev_fused
         _convnext.TRAIN_FUSED_KERNEL = prev_kernel
+        _pspnet.TRAIN_CRITERION = prev_psp
 
 
 if __name__ == "__main__":
