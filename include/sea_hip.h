@@ -669,6 +669,32 @@ int sea_msf_accumulate(const float* logits, float* score, int B, int C, int hl, 
                        int flip, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * K11 sliding-window evaluation (semseg.utils.segmenter_eval), replacing merge_windows of
+ * semseg/utils/segmenter_eval.py:51-92: logit[:, ha:ha+ws, wa:wa+ws] += window and count += 1 over the windows,
+ * logit / count, interpolate(ori_shape, bilinear, align_corners=False), [flip along W], softmax(dim=0).
+ * sea_sw_merge: logits (B * n_h * n_w, C, hl, wl), image-major (window ih * n_w + iw of image b is row
+ *   b * n_h * n_w + ih * n_w + iw); window (ih, iw) covers rows h_anchors[ih] .. + ws and columns w_anchors[iw] .. + ws
+ *   of the merged (H, W) image.  hl == ws and wl == ws: the model's output for the window; smaller: its forward_lowres
+ *   output, up-sampled to (ws, ws) on the fly at the window-local coordinate with M2's align_corners=False rule and
+ *   rounding (the window logits are never written).  Per merged pixel the covering windows' values are added in fp32
+ *   from 0.f, h anchor outer, w anchor inner, and divided by their number: the reference's operations in its order.
+ *   softmax == 0: out (B, C, H, W) = the averaged logits (flip and accumulate must be 0).
+ *   softmax != 0: out = (accumulate ? out : 0) + softmax over C of the averaged logits, output column x taking merged
+ *   column W-1-x when flip != 0; the averaged logits are never written.
+ *   h_anchors[n_h], w_anchors[n_w]: HOST arrays, copied into the kernel arguments (no device allocation); on each axis
+ *   1 .. SEA_SW_MAX_ANCHORS anchors, strictly ascending, the first 0, the last n - ws, consecutive ones at most ws apart.
+ *   C <= SEA_MSF_MAX_CLASSES, hl <= ws, wl <= ws, H*W < 2^31, B * n_h * n_w <= 65535.  out must not alias logits.
+ * sea_sw_finish: score (B, C, Ho, Wo) = (accumulate ? score : 0) + softmax over C of the align_corners=False bilinear
+ *   resize (ATen's rule, up or down) of avg (B, C, H, W), mirrored along W when flip != 0: the tail of merge_windows for
+ *   an original size that differs from the merged one.  score must not alias avg.
+ * No atomics: both are bitwise reproducible. */
+#define SEA_SW_MAX_ANCHORS 32
+int sea_sw_merge(const float* logits, float* out, int B, int C, int hl, int wl, int ws, const int* h_anchors, int n_h,
+                 const int* w_anchors, int n_w, int H, int W, int flip, int softmax, int accumulate, void* stream);
+int sea_sw_finish(const float* avg, float* score, int B, int C, int H, int W, int Ho, int Wo, int flip, int accumulate,
+                  void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * P1-P3: PSPNet-ResNet50 (semseg/models/ddcat_psp.py:372-486 with backbones/resnet_ddcat.py), the steps of its frozen
  * eval forward / input gradient that are not convolutions.  All fp32.
  * sea_psp_polyphase_split: x dense NHWC (B, H, W, C) -> y (B*P, ceil(H/d), ceil(W/d), C), P = d*d (first_only: P = 1,

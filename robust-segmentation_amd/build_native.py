@@ -50,6 +50,7 @@ SOURCES = [
     ("mlp_fused.hip", ["-fno-slp-vectorize"]),
     ("classifier.hip", []),
     ("msf_kernels.hip", ["-ffp-contract=off"]),
+    ("sw_kernels.hip", ["-ffp-contract=off"]),
     ("psp_kernels.hip", []),
     ("bn_train.hip", []),
     ("train_loss.hip", []),

@@ -141,6 +141,9 @@ _SIGS = {
     "sea_train_ce_up_pow2_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "sea_train_ce_up_pow2_fwd": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _vp]),
     "sea_train_ce_up_pow2_scale": (_i, [_vp, _vp, _vp, _vp, _i64, _vp]),
+    "sea_sw_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int), _i, _i, _i, _i, _i, _i,
+                          _vp]),
+    "sea_sw_finish": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -647,6 +650,75 @@ def msf_accumulate(logits, score, scaled_size, flip: bool = False):
     _check(lib().sea_msf_accumulate(_p(logits), _p(score), B, Cc, hl, wl, Hs, Ws, H, W, int(bool(flip)), _stream()),
            "sea_msf_accumulate")
     return score
+
+
+# ------------------------------------------------------------------------------------------------ K11
+SW_MAX_ANCHORS = 32       # SEA_SW_MAX_ANCHORS
+
+
+def _sw_out(name, out, shape, src, accumulate):
+    if out is None:
+        if accumulate:
+            raise SeaNativeError(f"{name}: accumulate needs the buffer to add to (out=)")
+        return torch.empty(shape, dtype=torch.float32, device=src.device)
+    _dev(out)
+    if tuple(out.shape) != shape:
+        raise SeaNativeError(f"{name}: output shape {tuple(out.shape)} != {shape}")
+    if out.data_ptr() == src.data_ptr():
+        raise SeaNativeError(f"{name}: out aliases the input")
+    return _f32c(out)
+
+
+def sw_merge(logits, window_size, h_anchors, w_anchors, size, *, softmax: bool = False, flip: bool = False, out=None,
+             accumulate: bool = False):
+    """Merge of sliding-window logits (reference semseg/utils/segmenter_eval.py:70-83): ``logits`` (B * n_win, C, hl, wl),
+    image-major, window ``ih * n_w + iw`` of an image at rows ``h_anchors[ih]``, columns ``w_anchors[iw]`` of the merged
+    ``size`` = (H, W); per pixel the fp32 sum of the covering windows in anchor order divided by their number.
+    ``hl == wl == window_size``: the model's output per window; smaller: its ``forward_lowres`` output, up-sampled inside
+    the kernel with the model's align_corners=False rule.  ``softmax=False`` returns the averaged logits (B, C, H, W);
+    ``softmax=True`` returns (or, with ``accumulate``, adds to ``out``) softmax_C of them, mirrored along W when ``flip``,
+    without writing the averaged logits."""
+    _dev(logits, out)
+    logits = _f32c(logits)
+    if logits.dim() != 4:
+        raise SeaNativeError(f"sw_merge: expected (B * n_win, C, hl, wl), got {tuple(logits.shape)}")
+    ha, wa = [int(a) for a in h_anchors], [int(a) for a in w_anchors]
+    n_h, n_w = len(ha), len(wa)
+    if not (1 <= n_h <= SW_MAX_ANCHORS and 1 <= n_w <= SW_MAX_ANCHORS):
+        raise SeaNativeError(f"sw_merge: {n_h} x {n_w} anchors, 1 .. {SW_MAX_ANCHORS} per axis are supported")
+    N_, Cc, hl, wl = logits.shape
+    ws, (H, W) = int(window_size), (int(size[0]), int(size[1]))
+    if N_ % (n_h * n_w):
+        raise SeaNativeError(f"sw_merge: {N_} window logits are no multiple of {n_h} x {n_w} windows per image")
+    B = N_ // (n_h * n_w)
+    if Cc > MSF_MAX_CLASSES:
+        raise SeaNativeError(f"sw_merge: {Cc} classes > {MSF_MAX_CLASSES}")
+    if hl > ws or wl > ws:
+        raise SeaNativeError(f"sw_merge: logits {hl}x{wl} larger than the window {ws}")
+    if (flip or accumulate) and not softmax:
+        raise SeaNativeError("sw_merge: flip / accumulate belong to the softmax epilogue")
+    out = _sw_out("sw_merge", out, (B, Cc, H, W), logits, accumulate)
+    _check(lib().sea_sw_merge(_p(logits), _p(out), B, Cc, hl, wl, ws, (C.c_int * n_h)(*ha), n_h, (C.c_int * n_w)(*wa), n_w,
+                              H, W, int(bool(flip)), int(bool(softmax)), int(bool(accumulate)), _stream()), "sea_sw_merge")
+    return out
+
+
+def sw_finish(avg, out_size, *, flip: bool = False, out=None, accumulate: bool = False):
+    """softmax_C(flip?(F.interpolate(avg, out_size, mode="bilinear", align_corners=False))) of averaged logits
+    (B, C, H, W): the tail of the reference's ``merge_windows`` when the original size differs from the merged one.
+    Written to, or with ``accumulate`` added to, ``out`` (B, C, Ho, Wo)."""
+    _dev(avg, out)
+    avg = _f32c(avg)
+    if avg.dim() != 4:
+        raise SeaNativeError(f"sw_finish: expected (B, C, H, W), got {tuple(avg.shape)}")
+    B, Cc, H, W = avg.shape
+    Ho, Wo = int(out_size[0]), int(out_size[1])
+    if Cc > MSF_MAX_CLASSES:
+        raise SeaNativeError(f"sw_finish: {Cc} classes > {MSF_MAX_CLASSES}")
+    out = _sw_out("sw_finish", out, (B, Cc, Ho, Wo), avg, accumulate)
+    _check(lib().sea_sw_finish(_p(avg), _p(out), B, Cc, H, W, Ho, Wo, int(bool(flip)), int(bool(accumulate)), _stream()),
+           "sea_sw_finish")
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ P1-P3 (PSPNet)

@@ -19,9 +19,10 @@ from . import _native as N
 from . import attacker as _A
 from .attacker import _FrozenParameters
 from .metrics import Metrics
+from .utils.segmenter_eval import inference as _sw_inference
 
-__all__ = ["Pgd_Attack", "Pgd_Attack_1", "evaluate", "evaluate_msf", "msf_scaled_size", "losses", "js_loss",
-           "masked_cross_entropy"]
+__all__ = ["Pgd_Attack", "Pgd_Attack_1", "evaluate", "evaluate_msf", "evaluate_sliding", "msf_scaled_size", "losses",
+           "js_loss", "masked_cross_entropy"]
 
 
 def js_loss(p, q, reduction="mean"):
@@ -358,6 +359,55 @@ def evaluate_msf(model, dataloader, device, scales, flip, n_classes=None, ignore
     ``acc, macc = metrics.compute_pixel_acc()`` but metrics.py:49-60 returns three values, so the reference raises
     ValueError after evaluating everything; no reference entry point calls it.  This returns the tuple the code intends."""
     metrics = _evaluate_msf_metrics(model, dataloader, device, scales, flip, n_classes, ignore_label, n_batches)
+    acc, macc, _ = metrics.compute_pixel_acc()
+    f1, mf1 = metrics.compute_f1()
+    ious, miou = metrics.compute_iou()
+    return acc, macc, f1, mf1, ious, miou
+
+
+# ---- sliding-window evaluation (semseg/utils/segmenter_eval.py) ----------------------------------------------------------
+@torch.no_grad()
+def _evaluate_sliding_metrics(model, dataloader, device, window_size, window_stride, batch_size=None, flip=False,
+                              n_classes=None, ignore_label=None, n_batches=-1):
+    ds = getattr(dataloader, "dataset", None)
+    if n_classes is None:
+        n_classes = ds.n_classes
+    if ignore_label is None:
+        ignore_label = ds.ignore_label if ds is not None and hasattr(ds, "ignore_label") else -1
+    n_classes = int(n_classes)
+    if n_classes > N.MSF_MAX_CLASSES:
+        raise ValueError(f"evaluate_sliding supports up to {N.MSF_MAX_CLASSES} classes, got {n_classes}")
+    device = torch.device(device)
+    model.eval()
+    metrics = Metrics(n_classes, ignore_label, device)
+    for i, batch in enumerate(dataloader):
+        images = batch[0].to(device).float().contiguous()
+        labels = batch[1].to(device)
+        B, H, W = labels.shape
+        score = _score_buffer(model, (B, n_classes, H, W), device)
+        bs = int(batch_size) if batch_size else B
+        _sw_inference(model, images, window_size, window_stride, bs, ori_shape=(H, W), n_cls=n_classes, flip=False,
+                      out=score, accumulate=False)
+        if flip:                                 # plain first, then the mirrored pass onto the same scores
+            _sw_inference(model, images, window_size, window_stride, bs, ori_shape=(H, W), n_cls=n_classes, flip=True,
+                          out=score, accumulate=True)
+        metrics.update(score, labels)            # K2 (argmax) + K3 (confusion)
+        if i + 1 == n_batches:
+            break
+    return metrics
+
+
+def evaluate_sliding(model, dataloader, device, window_size, window_stride, batch_size=None, flip=False, n_classes=None,
+                     ignore_label=None, n_batches=-1):
+    """Sliding-window clean evaluation (semseg/utils/segmenter_eval.py): the loop of ``evaluate_msf`` with
+    ``semseg.utils.segmenter_eval.inference`` per batch -- images whose short side is below ``window_size`` are up-scaled,
+    covered with ``window_size`` windows at ``window_stride``, the window logits are averaged where they overlap (K11a) and
+    brought to the label size as probabilities (K11b when that size differs).  ``batch_size`` windows go through the model
+    at a time (default: the loader's batch size).  With ``flip`` the plain and the mirrored pass are summed into one fp32
+    score buffer, plain first.  ``n_classes`` / ``ignore_label`` / ``n_batches`` and the returned
+    ``(acc, macc, f1, mf1, ious, miou)`` are ``evaluate_msf``'s."""
+    metrics = _evaluate_sliding_metrics(model, dataloader, device, window_size, window_stride, batch_size, flip, n_classes,
+                                        ignore_label, n_batches)
     acc, macc, _ = metrics.compute_pixel_acc()
     f1, mf1 = metrics.compute_f1()
     ious, miou = metrics.compute_iou()
