@@ -306,6 +306,23 @@ int sea_upsample_bilinear_nhwc_fwd(const float* x, const float* residual, float*
                                    int w, int H, int W, int64_t y_pixel_stride, void* stream);
 int sea_upsample_bilinear_nhwc_bwd(const float* gy, float* gx, int B, int C, int h, int w, int H, int W,
                                    int64_t gy_pixel_stride, void* stream);
+/* host only, touches no device: the kernel one of the four entries above, or sea_tap_gather_fwd / _bwd (M6), runs for these
+ * integers (csrc/upsample_plan.h).  op = SEA_UP_*; planes_or_batch = planes for the NCHW entries, B for the others; C and
+ * pixel_stride are read for NHWC (C for the tap gather too).  Only the alignment of the two addresses matters: src = what the
+ * kernel reads (x | residual, gy, G, gz), dst = what it writes.  general_only / xcd_order: the two words of
+ * sea_process_config that the entries themselves pass (SEA_UPSAMPLE_GENERAL, SEA_XCD_ORDER = 0 | 1 | 2).
+ * out[20] = kernel (enum UpsampleKernel of the plan header, in its order), S (template parameter, 0 = none), grid x, grid y,
+ * threads, dynamic LDS bytes, planes per launch and launches of the chunked general NCHW kernels, work items (low, high 32
+ * bits), the kernel's xcd argument, nt, lcols, RP, bands, per_xcd, TI, RMAX, nbh, nbw.  Returns 1 for exactly the integers
+ * for which the entry returns 1. */
+#define SEA_UP_NCHW_FWD 0
+#define SEA_UP_NCHW_BWD 1
+#define SEA_UP_NHWC_FWD 2
+#define SEA_UP_NHWC_BWD 3
+#define SEA_UP_TAP_FWD 4
+#define SEA_UP_TAP_BWD 5
+int sea_upsample_plan(int op, int64_t planes_or_batch, int C, int h, int w, int H, int W, int64_t pixel_stride,
+                      size_t src_addr, size_t dst_addr, int general_only, int xcd_order, int32_t out[20]);
 
 /* M4  (model side) Winograd F(m x m, 3 x 3) transforms, m = 2 or 4, for the 3x3 / stride 1 / pad 1
  * convolutions of the UperNet head (uperforseg.py:200-215 fpn_convs, 255-262 fpn_bottleneck), fp32 NHWC.

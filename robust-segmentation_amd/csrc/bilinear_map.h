@@ -37,12 +37,17 @@ __device__ __forceinline__ int first_dst_ge(int t, float r, int n_in, int n_out)
 // r = 1/S and every intermediate of axis_map_u are exact in float for such factors: identical results, integer ops only.
 // S = 0 selects the general float rule.
 template <int S>
+struct Pow2 {
+  static constexpr int LOG = S == 2 ? 1 : S == 4 ? 2 : S == 8 ? 3 : 4;
+  static_assert(S == 2 || S == 4 || S == 8 || S == 16, "supported factors");
+};
+
+template <int S>
 __device__ __forceinline__ AxisMapU axis_map_p2(int dst, float r, int n_in) {
   if constexpr (S == 0) {
     return axis_map_u(dst, r, n_in);
   } else {
-    static_assert(S == 2 || S == 4 || S == 8 || S == 16, "supported factors");
-    constexpr int LOG = S == 2 ? 1 : S == 4 ? 2 : S == 8 ? 3 : 4;
+    constexpr int LOG = Pow2<S>::LOG;
     const int t = dst + S / 2;
     AxisMapU m;
     m.i0 = (t >> LOG) - 1;
@@ -60,6 +65,14 @@ __device__ __forceinline__ AxisMapU axis_map_p2(int dst, float r, int n_in) {
 __device__ __forceinline__ float axis_coef(int dst, int src, float r, int n_in) {
   const AxisMapU m = axis_map_u(dst, r, n_in);
   return ((m.i0 == src) ? (1.f - m.lam) : 0.f) + ((m.i1 == src) ? m.lam : 0.f);
+}
+
+// ATen's expression tree of the four-tap sum (K2u, T2u): with it the fused criteria see F.interpolate's logits bit for bit.
+// Inline, so it is contracted under its includer's flags; both users are built with the default ones.
+__device__ __forceinline__ float lerp2(float v00, float v01, float v10, float v11, float lx, float ly) {
+  const float top = (1.f - lx) * v00 + lx * v01;
+  const float bot = (1.f - lx) * v10 + lx * v11;
+  return (1.f - ly) * top + ly * bot;
 }
 
 // ---- align_corners=True (ATen's UpSampleBilinear2d.cu): scale = (in-1)/(out-1) in fp32 (0 for out == 1),

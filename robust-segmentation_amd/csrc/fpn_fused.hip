@@ -14,6 +14,7 @@
 #include "sea_common.h"
 #include <utility>
 #include "bilinear_map.h"
+#include "upsample_plan.h"
 
 namespace sea {
 
@@ -21,7 +22,7 @@ namespace sea {
 // of one tap row / column touch at most 3 coarse rows / columns, so per tap a 3x3 coarse window (9 loads) feeds all
 // 16 outputs through separable weights: 81 loads per 16 outputs instead of 36 per output (the plain gather was
 // bound by L2 bandwidth at 16 TB/s of corner re-reads).
-constexpr int kTB = 4;
+constexpr int kTB = kTapBlock;  // (upsample_plan.h: the plan counts the blocks)
 
 // ---- interior blocks of a power-of-two factor: every weight is a compile-time constant ----------------------------------
 // For S = 4 / 8 the sample rows P = Y0 + q + a - 1 of a 4 x 4 block (Y0 a multiple of 4, phase Y0 mod S) map to
@@ -44,7 +45,7 @@ __device__ __forceinline__ void tg_static_for(F&& f) {
 
 template <int S>
 struct TgAxis {   // one axis of one tap: u0 = phase + a - 1 + S / 2
-  static constexpr int LOG = S == 4 ? 2 : 3;
+  static constexpr int LOG = Pow2<S>::LOG;
   static constexpr int base(int u0) { return (u0 >> LOG) - 1; }                               // ib - c
   static constexpr int k(int u0, int q) { return ((u0 + q) >> LOG) - (u0 >> LOG); }          // i0 - ib: 0 or 1
   static constexpr float lam(int u0, int q) { return ((float)((u0 + q) & (S - 1)) + 0.5f) / (float)S; }
@@ -344,54 +345,37 @@ __global__ __launch_bounds__(256) void gate_scale_kernel(const float4* __restric
 
 using namespace sea;
 
+// The two tap-gather entries choose by the same rule as M2's: pointers, query, plan (upsample_plan.h), launch.
 // G (B,h,w,9,C) coarse per-tap maps -> extra (B,H,W,C) (+)= sum over the 3x3 taps of the shifted up-samplings
 // inner: 0 switches the compile-time-weight path of interior blocks off (A/B; the shipped value is 1)
 extern "C" int sea_tap_gather_fwd(const float* G, float* extra, int accumulate, int B, int C, int h, int w, int H, int W,
                                   int inner, void* stream) {
-  SEA_CHECK_ARG(G && extra && B > 0 && C > 0 && (C % 4) == 0 && h > 0 && w > 0);
-  // the 3x3 coarse window per tap covers 4 consecutive sample positions only for factors >= 3
-  SEA_CHECK_ARG((int64_t)H >= 3 * (int64_t)h && (int64_t)W >= 3 * (int64_t)w);
-  SEA_CHECK_ARG(((((uintptr_t)G) | ((uintptr_t)extra)) & 15) == 0);
-  const int nBh = (H + kTB - 1) / kTB, nBw = (W + kTB - 1) / kTB;
-  const int64_t total = (int64_t)B * nBh * nBw * (C / 4);
-  // the kernel indexes inside one image with 32-bit offsets
-  SEA_CHECK_ARG((int64_t)H * W * (C / 4) < (1ll << 31) && (int64_t)h * w * 9 * (C / 4) < (1ll << 31));
-  const int general_only = process_config().upsample_general;
-  const int inner_ok = inner ? 1 : 0;
-#define SEA_LAUNCH_TAP_FWD(SS)                                                                                          \
-  hipLaunchKernelGGL(tap_gather_fwd_kernel<SS>, dim3(grid_for_xcd(total, 256)), dim3(256), 0, (hipStream_t)stream,      \
-                     (const float4*)G, (float4*)extra, accumulate, C / 4, h, w, H, W, (float)h / (float)H,              \
-                     (float)w / (float)W, nBh, nBw, total, xcd_order_enabled(), divs3(C / 4, nBw, nBh), inner_ok)
-  if (!general_only && (int64_t)h * 4 == H && (int64_t)w * 4 == W) {
-    SEA_LAUNCH_TAP_FWD(4);
-  } else if (!general_only && (int64_t)h * 8 == H && (int64_t)w * 8 == W) {
-    SEA_LAUNCH_TAP_FWD(8);
-  } else {
-    SEA_LAUNCH_TAP_FWD(0);
-  }
-#undef SEA_LAUNCH_TAP_FWD
+  SEA_CHECK_ARG(G && extra);
+  UpsamplePlan pl;
+  SEA_CHECK_ARG(upsample_plan(UpsampleQuery{SEA_UP_TAP_FWD, B, C, h, w, H, W, 0, (uintptr_t)G, (uintptr_t)extra,
+                                            process_config().upsample_general != 0, process_config().xcd_order}, &pl) == 0);
+  dispatch_s<0, 4, 8>(pl.S, [&](auto S) {
+    launch_planned(tap_gather_fwd_kernel<decltype(S)::value>, pl, 1, stream, (const float4*)G, (float4*)extra, accumulate, C / 4,
+                   h, w, H, W, (float)h / (float)H, (float)w / (float)W, pl.nbh, pl.nbw, pl.total, pl.xo,
+                   divs3(C / 4, pl.nbw, pl.nbh), inner ? 1 : 0);
+  });
   SEA_RETURN_LAST();
 }
 
 // gz (B,H,W,C) gradient at the convolution output -> dG (B,h,w,9,C)
 extern "C" int sea_tap_gather_bwd(const float* gz, float* dG, int B, int C, int h, int w, int H, int W, void* stream) {
-  SEA_CHECK_ARG(gz && dG && B > 0 && C > 0 && (C % 4) == 0 && h > 0 && w > 0 && H >= h && W >= w);
-  SEA_CHECK_ARG(((((uintptr_t)gz) | ((uintptr_t)dG)) & 15) == 0);
-  const int64_t total = (int64_t)B * h * w * (C / 4);
-  const int general_only = process_config().upsample_general;
-  if (!general_only && (int64_t)h * 4 == H && (int64_t)w * 4 == W) {
-    hipLaunchKernelGGL(tap_gather_bwd_pow2_kernel<4>, dim3(grid_for_xcd(total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const float4*)gz, (float4*)dG, C / 4, h, w, total, xcd_order_enabled(), divs3(C / 4, w, h));
-    SEA_RETURN_LAST();
-  }
-  if (!general_only && (int64_t)h * 8 == H && (int64_t)w * 8 == W) {
-    hipLaunchKernelGGL(tap_gather_bwd_pow2_kernel<8>, dim3(grid_for_xcd(total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const float4*)gz, (float4*)dG, C / 4, h, w, total, xcd_order_enabled(), divs3(C / 4, w, h));
-    SEA_RETURN_LAST();
-  }
-  hipLaunchKernelGGL(tap_gather_bwd_kernel, dim3(grid_for_xcd(total, 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const float4*)gz, (float4*)dG, C / 4, h, w, H, W, (float)h / (float)H, (float)w / (float)W, total,
-                     xcd_order_enabled(), divs3(C / 4, w, h));
+  SEA_CHECK_ARG(gz && dG);
+  UpsamplePlan pl;
+  SEA_CHECK_ARG(upsample_plan(UpsampleQuery{SEA_UP_TAP_BWD, B, C, h, w, H, W, 0, (uintptr_t)gz, (uintptr_t)dG,
+                                            process_config().upsample_general != 0, process_config().xcd_order}, &pl) == 0);
+  if (pl.kernel == UPK_TAP_BWD_POW2)
+    dispatch_s<4, 8>(pl.S, [&](auto S) {
+      launch_planned(tap_gather_bwd_pow2_kernel<decltype(S)::value>, pl, 1, stream, (const float4*)gz, (float4*)dG, C / 4, h, w,
+                     pl.total, pl.xo, divs3(C / 4, w, h));
+    });
+  else
+    launch_planned(tap_gather_bwd_kernel, pl, 1, stream, (const float4*)gz, (float4*)dG, C / 4, h, w, H, W, (float)h / (float)H,
+                   (float)w / (float)W, pl.total, pl.xo, divs3(C / 4, w, h));
   SEA_RETURN_LAST();
 }
 

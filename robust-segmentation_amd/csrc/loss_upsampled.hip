@@ -21,6 +21,7 @@
 // clamped at 0, i0 = floor(src), i1 = min(i0+1, n-1), lambda = src-i0,
 // val = (1-ly)*((1-lx)*v00 + lx*v01) + ly*((1-lx)*v10 + lx*v11).  Any (non-integer) scale works.
 #include "sea_common.h"
+#include "bilinear_map.h"
 
 namespace sea {
 
@@ -30,39 +31,6 @@ struct __attribute__((aligned(16))) BlockPartialU {
   float loss, track;
   int n_correct, pad;
 };
-
-struct AxisMap {
-  int i0, i1;
-  float lam;
-};
-
-__device__ __forceinline__ AxisMap axis_map(int dst, float r, int n_in) {
-  float src = r * ((float)dst + 0.5f) - 0.5f;
-  src = src < 0.f ? 0.f : src;
-  AxisMap m;
-  m.i0 = (int)src;
-  if (m.i0 > n_in - 1) m.i0 = n_in - 1;
-  m.i1 = m.i0 + ((m.i0 < n_in - 1) ? 1 : 0);
-  m.lam = src - (float)m.i0;
-  return m;
-}
-
-// smallest dst in [0, n_out] whose i0 >= t  (i0 is non-decreasing in dst)
-__device__ __forceinline__ int first_dst_with_i0_ge(int t, float r, int n_in, int n_out) {
-  if (t <= 0) return 0;
-  if (t > n_in - 1) return n_out;
-  int d = (int)ceilf(((float)t + 0.5f) / r - 0.5f);
-  d = d < 0 ? 0 : (d > n_out ? n_out : d);
-  while (d > 0 && axis_map(d - 1, r, n_in).i0 >= t) --d;
-  while (d < n_out && axis_map(d, r, n_in).i0 < t) ++d;
-  return d;
-}
-
-__device__ __forceinline__ float lerp2(float v00, float v01, float v10, float v11, float lx, float ly) {
-  const float top = (1.f - lx) * v00 + lx * v01;
-  const float bot = (1.f - lx) * v10 + lx * v11;
-  return (1.f - ly) * top + ly * bot;
-}
 
 __device__ __forceinline__ float loss_value_u(int mode, bool valid, bool correct, float ce, float logp, float py,
                                               float l1p, float wy) {
@@ -105,10 +73,10 @@ __global__ __launch_bounds__(256) void loss_upsampled_kernel(
   const int ya = blockIdx.y * TL, xa = blockIdx.x * TL;             // owned low-res tile origin
   const int yb = min(ya + TL, h), xb = min(xa + TL, wl);
   // full-res region: rows whose i0 in [ya-1, yb) ; owned rows: i0 in [ya, yb)
-  const int Y0e = first_dst_with_i0_ge(ya - 1, rh, h, H), Y0o = first_dst_with_i0_ge(ya, rh, h, H);
-  const int Y1 = first_dst_with_i0_ge(yb, rh, h, H);
-  const int X0e = first_dst_with_i0_ge(xa - 1, rw, wl, W), X0o = first_dst_with_i0_ge(xa, rw, wl, W);
-  const int X1 = first_dst_with_i0_ge(xb, rw, wl, W);
+  const int Y0e = first_dst_ge(ya - 1, rh, h, H), Y0o = first_dst_ge(ya, rh, h, H);
+  const int Y1 = first_dst_ge(yb, rh, h, H);
+  const int X0e = first_dst_ge(xa - 1, rw, wl, W), X0o = first_dst_ge(xa, rw, wl, W);
+  const int X1 = first_dst_ge(xb, rw, wl, W);
   const int RH = Y1 - Y0e, RW = X1 - X0e;  // <= RMAX by construction of the launcher
 
   // ---- phase 0: low-res tile (rows ya-1 .. yb, clamped into the image) and axis tables -------------
@@ -122,21 +90,21 @@ __global__ __launch_bounds__(256) void loss_upsampled_kernel(
     lowt[i] = lowb[((int64_t)c * h + gy) * wl + gx];
   }
   for (int i = threadIdx.x; i < RH; i += 256) {
-    const AxisMap m = axis_map(Y0e + i, rh, h);
+    const AxisMapU m = axis_map_u(Y0e + i, rh, h);
     r_i0[i] = m.i0 - (ya - 1);
     r_i1[i] = m.i1 - (ya - 1);
     r_lam[i] = m.lam;
   }
   for (int i = threadIdx.x; i < RW; i += 256) {
-    const AxisMap m = axis_map(X0e + i, rw, wl);
+    const AxisMapU m = axis_map_u(X0e + i, rw, wl);
     c_i0[i] = m.i0 - (xa - 1);
     c_i1[i] = m.i1 - (xa - 1);
     c_lam[i] = m.lam;
   }
   if (threadIdx.x < TL + 3) {
     const int t = threadIdx.x;  // local cell index: global source index ya-1+t
-    rbeg[t] = min(max(first_dst_with_i0_ge(ya - 1 + t, rh, h, H), Y0e), Y1) - Y0e;
-    cbeg[t] = min(max(first_dst_with_i0_ge(xa - 1 + t, rw, wl, W), X0e), X1) - X0e;
+    rbeg[t] = min(max(first_dst_ge(ya - 1 + t, rh, h, H), Y0e), Y1) - Y0e;
+    cbeg[t] = min(max(first_dst_ge(xa - 1 + t, rw, wl, W), X0e), X1) - X0e;
   }
   __syncthreads();
 
@@ -353,7 +321,7 @@ __global__ __launch_bounds__(256) void loss_upsampled_finalize(const BlockPartia
 //     reproducible.  Labels and arg-max bytes of a cell row travel as one wave access (lane = pixel of the row).
 //   * no LDS in the main kernel, ~70 registers: eight waves per SIMD; corner vectors are gathered straight from the planes
 //     (64 lines per wave access, 2 x NS accesses per cell of S^2 pixels, prefetched one cell ahead).
-// Interpolation arithmetic is ATen's expression tree (lerp2 above), so the logits equal F.interpolate's bit for bit.
+// Interpolation arithmetic is ATen's expression tree (lerp2 of bilinear_map.h), so the logits equal F.interpolate's bit for bit.
 __device__ __forceinline__ float dpp_max16(float v) {   // max over the 16 lanes of a DPP row, in every lane
   v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true)));   // quad_perm [1,0,3,2]
   v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true)));   // quad_perm [2,3,0,1]

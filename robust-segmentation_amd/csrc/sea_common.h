@@ -4,9 +4,10 @@
 #include <stdint.h>
 #include <stdlib.h>
 
-#include "../../include/sea_hip.h"
+#include <type_traits>
 
-#define SEA_ERR_ARG 1  // == hipErrorInvalidValue
+#include "../../include/sea_hip.h"
+#include "launch_grid.h"  // SEA_ERR_ARG, grid_for, grid_for_xcd
 
 #define SEA_CHECK_ARG(cond) \
   do {                      \
@@ -22,21 +23,13 @@
 namespace sea {
 
 constexpr int kWave = 64;          // CDNA wavefront
-constexpr int kMaxGridX = 256 * 8; // memory-bound launches: <= 8 blocks per CU, grid-stride beyond
-
-static inline int grid_for(int64_t work_items, int block) {
-  int64_t g = (work_items + block - 1) / block;
-  if (g < 1) g = 1;
-  if (g > kMaxGridX) g = kMaxGridX;
-  return (int)g;
-}
 
 // ---- XCD-aware work order for grid-stride kernels with spatial reuse -------------------------------------------------
 // The dispatcher deals consecutive block ids round-robin to the 8 XCDs, each with a private 4 MB L2.  A kernel whose
 // neighbouring work items read overlapping input (stencils, bilinear footprints, Winograd tiles) therefore fetches every
 // shared pixel once per XCD from the fabric.  xcd_range() gives XCD k the k-th contiguous eighth of the linear index
 // space (one image at B = 8) and lets the blocks that landed on that XCD stride through it: overlapping reads meet in
-// one L2.  The launch must use grid_for_xcd() (a multiple of 8 blocks).  SEA_XCD_ORDER=0 restores the plain order.
+// one L2.  The launch must use grid_for_xcd() (launch_grid.h: a multiple of 8 blocks).  SEA_XCD_ORDER=0 restores the plain order.
 //
 // The library's only configuration that is not an argument of a call: two A/B switches that dozens of launchers consult.  Read
 // from the environment once, at first use, and never written again (api_misc.cpp, the one place the library reads the
@@ -49,9 +42,18 @@ const ProcessConfig& process_config();
 
 static inline int xcd_order_enabled() { return process_config().xcd_order; }
 
-static inline int grid_for_xcd(int64_t work_items, int block) {
-  const int g = grid_for(work_items, block);
-  return (g + 7) / 8 * 8;
+// ---- launchers that take a plan (upsample_plan.h) -------------------------------------------------------------------------
+// The one instantiation switch: f(std::integral_constant<int, S>) for the run-time S if it is one of the listed template
+// values; false (nothing called) otherwise, which a plan never names.
+template <int... Ss, typename F>
+static inline bool dispatch_s(int S, F&& f) {
+  return ((S == Ss ? (f(std::integral_constant<int, Ss>{}), true) : false) || ...);
+}
+
+// grid (x, y), block and dynamic LDS are the plan's; z = the planes of this launch
+template <typename Plan, typename Kernel, typename... Args>
+static inline void launch_planned(Kernel kernel, const Plan& pl, int z, void* stream, Args... args) {
+  hipLaunchKernelGGL(kernel, dim3(pl.grid_x, pl.grid_y, z), dim3(pl.threads), pl.lds, (hipStream_t)stream, args...);
 }
 
 // ---- division by a launch-time constant: 3 instructions instead of the ~100 of a 64-bit (or ~25 of a 32-bit) integer

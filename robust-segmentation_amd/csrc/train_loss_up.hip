@@ -41,13 +41,6 @@ constexpr int kUpMinClasses = 2, kUpMaxClasses = 192;  // K2u's ceiling (and MSF
 constexpr size_t kUpLdsBudget = 64 * 1024;
 constexpr int kUpMaxRegion = 72;
 
-// ATen's expression tree (K2u: lerp2)
-__device__ __forceinline__ float lerp2(float v00, float v01, float v10, float v11, float lx, float ly) {
-  const float top = (1.f - lx) * v00 + lx * v01;
-  const float bot = (1.f - lx) * v10 + lx * v11;
-  return (1.f - ly) * top + ly * bot;
-}
-
 // The two interpolation rules the kernels are instantiated for.  map: source pair and weight of a destination index;
 // first_ge: its inverse (first destination index whose i0 is >= t); lerp: the rule's expression tree; scale: the float
 // the launcher passes as rh / rw.

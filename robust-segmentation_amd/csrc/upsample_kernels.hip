@@ -14,6 +14,7 @@
 // Source-index rule = ATen: src = r*(dst+0.5)-0.5 clamped at 0, i0=floor(src), i1=min(i0+1,n-1).
 #include "sea_common.h"
 #include "bilinear_map.h"
+#include "upsample_plan.h"
 
 namespace sea {
 
@@ -161,12 +162,6 @@ struct FVec<2> {
 template <>
 struct FVec<4> {
   using type = float4;
-};
-
-template <int S>
-struct Pow2 {
-  static constexpr int LOG = S == 2 ? 1 : S == 4 ? 2 : S == 8 ? 3 : 4;
-  static_assert(S == 2 || S == 4 || S == 8 || S == 16, "supported factors");
 };
 
 // One lane = one float4 of the output.  Groups of G = min(4, S/2) consecutive pixels share their source columns:
@@ -456,39 +451,11 @@ __global__ __launch_bounds__(256) void upsample_bwd_rows_kernel(const float* __r
   }
 }
 
-// integer power-of-two factor in both axes (2, 4, 8, 16), 0 otherwise
-static inline int pow2_factor(int h, int w, int H, int W) {
-  for (int S = 2; S <= 16; S *= 2)
-    if ((int64_t)h * S == H && (int64_t)w * S == W) return S;
-  return 0;
-}
-
-static inline int upsample_general_only() { return process_config().upsample_general; }
-
 // ---- channels_last variants: x (B,h,w,C), y (B,H,W,C), C % 4 == 0 ------------------------------------------
 // Lanes run along the channel dimension (16-byte accesses, perfectly coalesced); no LDS.  The UperNet head
 // is channels_last end to end on ROCm (MIOpen's NHWC igemm kernels return that layout), so these variants
 // remove the layout copies around every up-sampling.
-// S > 0: power-of-two factor in both axes, integer source map (identical values, no float index arithmetic)
-template <int S>
-__device__ __forceinline__ AxisMapU nhwc_axis(int dst, float r, int n_in) {
-  if constexpr (S == 0) {
-    return axis_map_u(dst, r, n_in);
-  } else {
-    constexpr int LOG = Pow2<S>::LOG;
-    const int t = dst + S / 2;
-    AxisMapU m;
-    m.i0 = (t >> LOG) - 1;
-    m.lam = ((float)(t & (S - 1)) + 0.5f) * (1.f / (float)S);
-    if (m.i0 < 0) {
-      m.i0 = 0;
-      m.lam = 0.f;
-    }
-    m.i1 = min(m.i0 + 1, n_in - 1);
-    return m;
-  }
-}
-
+// S > 0: power-of-two factor in both axes, integer source map (axis_map_p2: identical values, no float index arithmetic)
 template <int S>
 __global__ __launch_bounds__(256) void upsample_nhwc_fwd_kernel(const float4* __restrict__ x,
                                                                 const float4* __restrict__ res, float4* __restrict__ y,
@@ -501,7 +468,7 @@ __global__ __launch_bounds__(256) void upsample_nhwc_fwd_kernel(const float4* __
     const int cg = ix.c0, X = ix.c1, Y = ix.c2;
     const int b = (int)ix.c3;
     const int64_t opix = ((int64_t)b * H + Y) * W + X;
-    const AxisMapU my = nhwc_axis<S>(Y, rh, h), mx = nhwc_axis<S>(X, rw, w);
+    const AxisMapU my = axis_map_p2<S>(Y, rh, h), mx = axis_map_p2<S>(X, rw, w);
     const float4* xb = x + (int64_t)b * h * w * CG + cg;
     const float4 v00 = xb[((int64_t)my.i0 * w + mx.i0) * CG], v01 = xb[((int64_t)my.i0 * w + mx.i1) * CG];
     const float4 v10 = xb[((int64_t)my.i1 * w + mx.i0) * CG], v11 = xb[((int64_t)my.i1 * w + mx.i1) * CG];
@@ -718,161 +685,99 @@ __global__ __launch_bounds__(256) void upsample_nhwc_bwd_pow2_kernel(const float
   }
 }
 
-static bool plan_bwd(int h, int w, int H, int W, int* TI, int* RMAX, size_t* lds) {
-  const double sh = (double)H / h, sw = (double)W / w;
-  const double s = sh > sw ? sh : sw;
-  // power-of-two input tiles (feature maps are powers of two: no ragged border tiles), region <= 80x80
-  // full-res pixels (~25 KB of LDS -> 6 workgroups per CU)
-  for (int t = 32; t >= 1; t >>= 1) {
-    const int rm = (int)((t + 1) * s) + 4;
-    const size_t b = sizeof(float) * ((size_t)rm * (rm + 1) + 4 * (size_t)rm + 2 * (size_t)(t + 3) + (size_t)rm * (t + 1));
-    if (rm <= 80 && b <= 48 * 1024) {
-      *TI = t;
-      *RMAX = rm;
-      *lds = b;
-      return true;
-    }
-  }
-  return false;
-}
-
 }  // namespace sea
 
 using namespace sea;
 
+// The four entries check their pointers, fill a query, take the plan (upsample_plan.h: kernel, template parameter, grid and
+// every scalar computed from the shape) and launch; they decide nothing.  dispatch_s finds every S a plan names.
+
 // x: (planes, h, w) -> y: (planes, H, W), H >= h, W >= w
-extern "C" int sea_upsample_bilinear_fwd(const float* x, float* y, int64_t planes, int h, int w, int H, int W,
-                                         void* stream) {
-  SEA_CHECK_ARG(x && y && planes > 0 && h > 0 && w > 0 && H >= h && W >= w);
-  const float rh = (float)h / (float)H, rw = (float)w / (float)W;
-  hipStream_t s = (hipStream_t)stream;
-  const int S = upsample_general_only() ? 0 : pow2_factor(h, w, H, W);
-  if (S && (((uintptr_t)y) & 15) == 0) {  // float4 stores: W % 4 == 0 and a 16-byte aligned base
-    if ((W & 3) == 0) {
-      if (S >= 4) {
-        const int64_t total = planes * (h + 1) * (W / 4);
-        const dim3 grid(grid_for_xcd(total, 256)), block(256);
-        const int xo = xcd_order_enabled() == 2;
-        const FastDiv fW4 = fast_div((uint32_t)(W / 4)), fC = fast_div((uint32_t)(h + 1));
-        const int nt = planes * H * W * 4 > (192ll << 20);   // non-temporal stores by output size
-        switch (S) {
-          case 4: hipLaunchKernelGGL(upsample_fwd_cells_kernel<4>, grid, block, 0, s, x, y, h, w, total, xo, fW4, fC, nt); break;
-          case 8: hipLaunchKernelGGL(upsample_fwd_cells_kernel<8>, grid, block, 0, s, x, y, h, w, total, xo, fW4, fC, nt); break;
-          default: hipLaunchKernelGGL(upsample_fwd_cells_kernel<16>, grid, block, 0, s, x, y, h, w, total, xo, fW4, fC, nt); break;
-        }
-        SEA_RETURN_LAST();
-      }
-      const int64_t total = planes * H * (W / 4);   // S == 2: one float4 per lane
-      const dim3 grid(grid_for_xcd(total, 256)), block(256);
-      // a pure output stream (the input is S^2 times smaller): the plain block order measured 10 % faster than the
-      // XCD-contiguous one (151 planes x 8, 128 -> 512: 341 vs 379 us); SEA_XCD_ORDER=2 forces the latter
-      const int xo = xcd_order_enabled() == 2;
-      const FastDiv fW4 = fast_div((uint32_t)(W / 4)), fH = fast_div((uint32_t)H);
-      hipLaunchKernelGGL(upsample_fwd_pow2_kernel<2>, grid, block, 0, s, x, y, h, w, total, xo, fW4, fH);
-      SEA_RETURN_LAST();
-    }
-  }
-  for (int64_t p0 = 0; p0 < planes; p0 += 65535) {
-    const int np = (int)((planes - p0) < 65535 ? (planes - p0) : 65535);
-    dim3 grid((W + 63) / 64, (H + 15) / 16, np);
-    hipLaunchKernelGGL(upsample_fwd_kernel, grid, dim3(256), 0, s, x + p0 * h * w, y + p0 * H * W, h, w, H, W, rh, rw);
-  }
+extern "C" int sea_upsample_bilinear_fwd(const float* x, float* y, int64_t planes, int h, int w, int H, int W, void* stream) {
+  SEA_CHECK_ARG(x && y);
+  UpsamplePlan pl;
+  SEA_CHECK_ARG(upsample_plan(UpsampleQuery{SEA_UP_NCHW_FWD, planes, 0, h, w, H, W, 0, (uintptr_t)x, (uintptr_t)y,
+                                            process_config().upsample_general != 0, process_config().xcd_order}, &pl) == 0);
+  if (pl.kernel == UPK_NCHW_FWD_CELLS)
+    dispatch_s<4, 8, 16>(pl.S, [&](auto S) {
+      launch_planned(upsample_fwd_cells_kernel<decltype(S)::value>, pl, 1, stream, x, y, h, w, pl.total, pl.xo,
+                     fast_div((uint32_t)(W / 4)), fast_div((uint32_t)(h + 1)), pl.nt);
+    });
+  else if (pl.kernel == UPK_NCHW_FWD_POW2)
+    launch_planned(upsample_fwd_pow2_kernel<2>, pl, 1, stream, x, y, h, w, pl.total, pl.xo, fast_div((uint32_t)(W / 4)),
+                   fast_div((uint32_t)H));
+  else
+    for (int64_t p0 = 0; p0 < planes; p0 += pl.chunk)
+      launch_planned(upsample_fwd_kernel, pl, (int)((planes - p0) < pl.chunk ? (planes - p0) : pl.chunk), stream,
+                     x + p0 * h * w, y + p0 * H * W, h, w, H, W, (float)h / (float)H, (float)w / (float)W);
   SEA_RETURN_LAST();
 }
 
 // gy: (planes, H, W) -> gx: (planes, h, w): gradient of sea_upsample_bilinear_fwd w.r.t. its input
-extern "C" int sea_upsample_bilinear_bwd(const float* gy, float* gx, int64_t planes, int h, int w, int H, int W,
-                                         void* stream) {
-  SEA_CHECK_ARG(gy && gx && planes > 0 && h > 0 && w > 0 && H >= h && W >= w);
-  {
-    const int S = upsample_general_only() ? 0 : pow2_factor(h, w, H, W);
-    // vector loads of min(4, S/2) floats at multiples of S/2 floats from the row start: rows must keep that alignment
-    const int VL = S / 2 >= 4 ? 4 : S / 2;
-    const int cols = W / 4;
-    if (S && (W & 3) == 0 && (cols == 32 || cols == 64 || cols == 128 || cols == 256) &&
-        (((uintptr_t)gy) & 15) == 0 && planes < (1 << 24)) {
-      int lcols = 5;
-      while ((1 << lcols) < cols) ++lcols;
-      const int nsub = 256 / cols;
-      const int RP = 16 / S > 2 ? 16 / S : 2;                  // input rows per sub-band: ~5 cells of S rows each
-      const int bands = (h + nsub * RP - 1) / (nsub * RP);
-      const int64_t units64 = planes * bands;
-      if (units64 < (1ll << 30)) {
-        const int units = (int)units64;
-        const int per_xcd = xcd_order_enabled() ? (units + 7) / 8 : 0;
-        const dim3 grid(per_xcd ? per_xcd * 8 : units), block(256);
-        hipStream_t s = (hipStream_t)stream;
-        switch (S) {
-          case 2: hipLaunchKernelGGL(upsample_bwd_rows_kernel<2>, grid, block, 0, s, gy, gx, h, w, lcols, RP, bands, units, per_xcd); break;
-          case 4: hipLaunchKernelGGL(upsample_bwd_rows_kernel<4>, grid, block, 0, s, gy, gx, h, w, lcols, RP, bands, units, per_xcd); break;
-          case 8: hipLaunchKernelGGL(upsample_bwd_rows_kernel<8>, grid, block, 0, s, gy, gx, h, w, lcols, RP, bands, units, per_xcd); break;
-          default: hipLaunchKernelGGL(upsample_bwd_rows_kernel<16>, grid, block, 0, s, gy, gx, h, w, lcols, RP, bands, units, per_xcd); break;
-        }
-        SEA_RETURN_LAST();
-      }
-    }
-    if (S && (((uintptr_t)gy) & (VL * 4 - 1)) == 0 && (W % (VL > 1 ? VL : 1)) == 0) {
-      const int64_t total = planes * h * w;
-      const dim3 grid(grid_for_xcd(total, 256)), block(256);
-      const int xo = xcd_order_enabled() == 2;  // plain order measured faster (386 vs 411 us at x4, 151 planes x 8)
-      const FastDiv fw = fast_div((uint32_t)w), fh = fast_div((uint32_t)h);
-      hipStream_t s = (hipStream_t)stream;
-      switch (S) {
-        case 2: hipLaunchKernelGGL(upsample_bwd_pow2_kernel<2>, grid, block, 0, s, gy, gx, h, w, total, xo, fw, fh); break;
-        case 4: hipLaunchKernelGGL(upsample_bwd_pow2_kernel<4>, grid, block, 0, s, gy, gx, h, w, total, xo, fw, fh); break;
-        case 8: hipLaunchKernelGGL(upsample_bwd_pow2_kernel<8>, grid, block, 0, s, gy, gx, h, w, total, xo, fw, fh); break;
-        default: hipLaunchKernelGGL(upsample_bwd_pow2_kernel<16>, grid, block, 0, s, gy, gx, h, w, total, xo, fw, fh); break;
-      }
-      SEA_RETURN_LAST();
-    }
-  }
-  int TI, RMAX;
-  size_t lds;
-  SEA_CHECK_ARG(plan_bwd(h, w, H, W, &TI, &RMAX, &lds));
-  const float rh = (float)h / (float)H, rw = (float)w / (float)W;
-  hipStream_t s = (hipStream_t)stream;
-  for (int64_t p0 = 0; p0 < planes; p0 += 65535) {
-    const int np = (int)((planes - p0) < 65535 ? (planes - p0) : 65535);
-    dim3 grid((w + TI - 1) / TI, (h + TI - 1) / TI, np);
-    hipLaunchKernelGGL(upsample_bwd_kernel, grid, dim3(256), lds, s, gy + p0 * H * W, gx + p0 * h * w, h, w, H, W, rh,
-                       rw, TI, RMAX);
-  }
+extern "C" int sea_upsample_bilinear_bwd(const float* gy, float* gx, int64_t planes, int h, int w, int H, int W, void* stream) {
+  SEA_CHECK_ARG(gy && gx);
+  UpsamplePlan pl;
+  SEA_CHECK_ARG(upsample_plan(UpsampleQuery{SEA_UP_NCHW_BWD, planes, 0, h, w, H, W, 0, (uintptr_t)gy, (uintptr_t)gx,
+                                            process_config().upsample_general != 0, process_config().xcd_order}, &pl) == 0);
+  if (pl.kernel == UPK_NCHW_BWD_ROWS)
+    dispatch_s<2, 4, 8, 16>(pl.S, [&](auto S) {
+      launch_planned(upsample_bwd_rows_kernel<decltype(S)::value>, pl, 1, stream, gy, gx, h, w, pl.lcols, pl.RP, pl.bands,
+                     (int)pl.total, pl.per_xcd);
+    });
+  else if (pl.kernel == UPK_NCHW_BWD_POW2)
+    dispatch_s<2, 4, 8, 16>(pl.S, [&](auto S) {
+      launch_planned(upsample_bwd_pow2_kernel<decltype(S)::value>, pl, 1, stream, gy, gx, h, w, pl.total, pl.xo,
+                     fast_div((uint32_t)w), fast_div((uint32_t)h));
+    });
+  else
+    for (int64_t p0 = 0; p0 < planes; p0 += pl.chunk)
+      launch_planned(upsample_bwd_kernel, pl, (int)((planes - p0) < pl.chunk ? (planes - p0) : pl.chunk), stream,
+                     gy + p0 * H * W, gx + p0 * h * w, h, w, H, W, (float)h / (float)H, (float)w / (float)W, pl.TI, pl.RMAX);
   SEA_RETURN_LAST();
 }
 
-// channels_last: x (B,h,w,C) -> y (B,H,W,C) and the gradient w.r.t. x; C % 4 == 0, 16-byte aligned.
-// residual (nullable, dense (B,H,W,C)) is added to the up-sampled map.  y / gy may be a channel slice of a wider NHWC tensor: *_pixel_stride is the distance in floats between
-// consecutive pixels (>= C, % 4 == 0), so the op can write into / read from a concatenation buffer in place.
+// channels_last: x (B,h,w,C) -> y (B,H,W,C) and the gradient w.r.t. x; C % 4 == 0, 16-byte aligned.  residual (nullable,
+// dense (B,H,W,C)) is added to the up-sampled map.  y / gy may be a channel slice of a wider NHWC tensor: *_pixel_stride is
+// the distance in floats between consecutive pixels (>= C, % 4 == 0): the op writes into / reads from a concatenation buffer.
 extern "C" int sea_upsample_bilinear_nhwc_fwd(const float* x, const float* residual, float* y, int B, int C, int h, int w,
                                               int H, int W, int64_t y_pixel_stride, void* stream) {
-  SEA_CHECK_ARG(x && y && B > 0 && C > 0 && (C % 4) == 0 && h > 0 && w > 0 && H >= h && W >= w);
-  SEA_CHECK_ARG(y_pixel_stride >= C && (y_pixel_stride % 4) == 0);
-  SEA_CHECK_ARG(((((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)residual)) & 15) == 0);
-  const int64_t total = (int64_t)B * H * W * (C / 4);
-  const int S = upsample_general_only() ? 0 : pow2_factor(h, w, H, W);
-#define SEA_LAUNCH_NHWC_FWD(SS)                                                                                         \
-  hipLaunchKernelGGL(upsample_nhwc_fwd_kernel<SS>, dim3(grid_for_xcd(total, 256 * 2)), dim3(256), 0,                   \
-                     (hipStream_t)stream, (const float4*)x, (const float4*)residual, (float4*)y, C / 4, h, w, H, W,     \
-                     (float)h / (float)H, (float)w / (float)W, total, y_pixel_stride / 4, xcd_order_enabled(),          \
-                     divs3(C / 4, W, H))
-  if (S == 2 || S == 4 || S == 8) {
-    const int64_t cells = (int64_t)B * (h + 1) * (w + 1) * (C / 4);
-#define SEA_LAUNCH_NHWC_FWD_CELLS(SS)                                                                                   \
-  hipLaunchKernelGGL(upsample_nhwc_fwd_cells_kernel<SS>, dim3(grid_for_xcd(cells, 256)), dim3(256), 0,                  \
-                     (hipStream_t)stream, (const float4*)x, (const float4*)residual, (float4*)y, C / 4, h, w, cells,    \
-                     y_pixel_stride / 4, xcd_order_enabled(), divs3(C / 4, w + 1, h + 1))
-    if (S == 2) {
-      SEA_LAUNCH_NHWC_FWD_CELLS(2);
-    } else if (S == 4) {
-      SEA_LAUNCH_NHWC_FWD_CELLS(4);
-    } else {
-      SEA_LAUNCH_NHWC_FWD_CELLS(8);
-    }
-#undef SEA_LAUNCH_NHWC_FWD_CELLS
-    SEA_RETURN_LAST();
-  }
-  if (S == 16) SEA_LAUNCH_NHWC_FWD(16); else SEA_LAUNCH_NHWC_FWD(0);
-#undef SEA_LAUNCH_NHWC_FWD
+  SEA_CHECK_ARG(x && y);
+  UpsamplePlan pl;
+  SEA_CHECK_ARG(upsample_plan(UpsampleQuery{SEA_UP_NHWC_FWD, B, C, h, w, H, W, y_pixel_stride,
+                                            (uintptr_t)x | (uintptr_t)residual, (uintptr_t)y,
+                                            process_config().upsample_general != 0, process_config().xcd_order}, &pl) == 0);
+  const float4 *x4 = (const float4*)x, *r4 = (const float4*)residual;
+  if (pl.kernel == UPK_NHWC_FWD_CELLS)
+    dispatch_s<2, 4, 8>(pl.S, [&](auto S) {
+      launch_planned(upsample_nhwc_fwd_cells_kernel<decltype(S)::value>, pl, 1, stream, x4, r4, (float4*)y, C / 4, h, w,
+                     pl.total, y_pixel_stride / 4, pl.xo, divs3(C / 4, w + 1, h + 1));
+    });
+  else
+    dispatch_s<0, 16>(pl.S, [&](auto S) {
+      launch_planned(upsample_nhwc_fwd_kernel<decltype(S)::value>, pl, 1, stream, x4, r4, (float4*)y, C / 4, h, w, H, W,
+                     (float)h / (float)H, (float)w / (float)W, pl.total, y_pixel_stride / 4, pl.xo, divs3(C / 4, W, H));
+    });
+  SEA_RETURN_LAST();
+}
+
+extern "C" int sea_upsample_bilinear_nhwc_bwd(const float* gy, float* gx, int B, int C, int h, int w, int H, int W,
+                                              int64_t gy_pixel_stride, void* stream) {
+  SEA_CHECK_ARG(gy && gx);
+  UpsamplePlan pl;
+  SEA_CHECK_ARG(upsample_plan(UpsampleQuery{SEA_UP_NHWC_BWD, B, C, h, w, H, W, gy_pixel_stride, (uintptr_t)gy, (uintptr_t)gx,
+                                            process_config().upsample_general != 0, process_config().xcd_order}, &pl) == 0);
+  const float4* g4 = (const float4*)gy;
+  const float rh = (float)h / (float)H, rw = (float)w / (float)W;
+  if (pl.kernel == UPK_NHWC_BWD_POW2)
+    dispatch_s<2, 4, 8>(pl.S, [&](auto S) {
+      launch_planned(upsample_nhwc_bwd_pow2_kernel<decltype(S)::value>, pl, 1, stream, g4, (float4*)gx, C / 4, h, w, pl.total,
+                     gy_pixel_stride / 4, pl.xo, divs3(C / 4, w, h));
+    });
+  else if (pl.kernel == UPK_NHWC_BWD_SMALL)
+    launch_planned(upsample_nhwc_bwd_small_kernel, pl, 1, stream, g4, (float4*)gx, C / 4, h, w, H, W, rh, rw, gy_pixel_stride / 4);
+  else
+    launch_planned(upsample_nhwc_bwd_kernel, pl, 1, stream, g4, (float4*)gx, C / 4, h, w, H, W, rh, rw, pl.total,
+                   gy_pixel_stride / 4, pl.xo, divs3(C / 4, w, h));
   SEA_RETURN_LAST();
 }
 
@@ -967,32 +872,3 @@ extern "C" int sea_adaptive_avg_pool_nhwc_bwd(const float* g, float* dx, int B, 
   SEA_RETURN_LAST();
 }
 
-extern "C" int sea_upsample_bilinear_nhwc_bwd(const float* gy, float* gx, int B, int C, int h, int w, int H, int W,
-                                              int64_t gy_pixel_stride, void* stream) {
-  SEA_CHECK_ARG(gy && gx && B > 0 && C > 0 && (C % 4) == 0 && h > 0 && w > 0 && H >= h && W >= w);
-  SEA_CHECK_ARG(gy_pixel_stride >= C && (gy_pixel_stride % 4) == 0);
-  SEA_CHECK_ARG(((((uintptr_t)gy) | ((uintptr_t)gx)) & 15) == 0);
-  const int64_t total = (int64_t)B * h * w * (C / 4);
-  const int S = upsample_general_only() ? 0 : pow2_factor(h, w, H, W);
-#define SEA_LAUNCH_NHWC_BWD(SS)                                                                                         \
-  hipLaunchKernelGGL(upsample_nhwc_bwd_pow2_kernel<SS>, dim3(grid_for_xcd(total, 256)), dim3(256), 0,                   \
-                     (hipStream_t)stream, (const float4*)gy, (float4*)gx, C / 4, h, w, total, gy_pixel_stride / 4,     \
-                     xcd_order_enabled(), divs3(C / 4, w, h))
-  if (S == 2) {
-    SEA_LAUNCH_NHWC_BWD(2);
-  } else if (S == 4) {
-    SEA_LAUNCH_NHWC_BWD(4);
-  } else if (S == 8) {
-    SEA_LAUNCH_NHWC_BWD(8);
-  } else if (total < 65536 && (int64_t)B * h * w < 65536) {
-    hipLaunchKernelGGL(upsample_nhwc_bwd_small_kernel, dim3(B * h * w, (C / 4 + 15) / 16), dim3(256), 0, (hipStream_t)stream,
-                       (const float4*)gy, (float4*)gx, C / 4, h, w, H, W, (float)h / (float)H, (float)w / (float)W,
-                       gy_pixel_stride / 4);
-  } else {
-    hipLaunchKernelGGL(upsample_nhwc_bwd_kernel, dim3(grid_for_xcd(total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const float4*)gy, (float4*)gx, C / 4, h, w, H, W, (float)h / (float)H, (float)w / (float)W,
-                       total, gy_pixel_stride / 4, xcd_order_enabled(), divs3(C / 4, w, h));
-  }
-#undef SEA_LAUNCH_NHWC_BWD
-  SEA_RETURN_LAST();
-}

@@ -82,6 +82,7 @@ _SIGS = {
     "sea_gate_scale": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp]),
     "sea_upsample_bilinear_nhwc_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i64, _vp]),
     "sea_upsample_bilinear_nhwc_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i64, _vp]),
+    "sea_upsample_plan": (_i, [_i, _i64, _i, _i, _i, _i, _i, _i64, _sz, _sz, _i, _i, C.POINTER(C.c_int32)]),
     "sea_patch2x2": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "sea_attention_bwd_terms": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                      _i64, _i64, _i64, _i, _vp]),
@@ -1043,6 +1044,33 @@ def upsample_bilinear_backward_cl(gy, in_size):
     _check(lib().sea_upsample_bilinear_nhwc_bwd(_p(gy), _p(gx), B, Cc, h, w, H, W, S, _stream()),
            "sea_upsample_bilinear_nhwc_bwd")
     return gx
+
+
+UPSAMPLE_OPS = ("nchw_fwd", "nchw_bwd", "nhwc_fwd", "nhwc_bwd", "tap_fwd", "tap_bwd")
+UPSAMPLE_KERNELS = ("nchw_fwd_general", "nchw_fwd_pow2", "nchw_fwd_cells", "nchw_bwd_general", "nchw_bwd_rows", "nchw_bwd_pow2",
+                    "nhwc_fwd", "nhwc_fwd_cells", "nhwc_bwd_general", "nhwc_bwd_small", "nhwc_bwd_pow2",
+                    "tap_fwd", "tap_bwd_general", "tap_bwd_pow2")
+_UPSAMPLE_PLAN_FIELDS = ("kernel", "S", "grid_x", "grid_y", "threads", "lds", "chunk", "nchunks", "total_lo", "total_hi", "xo", "nt",
+                         "lcols", "RP", "bands", "per_xcd", "TI", "RMAX", "nbh", "nbw")
+
+
+def upsample_plan(op: str, n: int, h: int, w: int, H: int, W: int, C_: int = 0, pixel_stride=None, src_addr: int = 0,
+                  dst_addr: int = 0, general_only=None, xcd_order=None) -> dict:
+    """Which kernel an M2 entry or the tap gather runs for these arguments (host only, no device; csrc/upsample_plan.h):
+    dict(rc, kernel in UPSAMPLE_KERNELS, S = its template parameter, grid_x / grid_y / threads / lds, chunk / nchunks, total,
+    and the launch scalars xo / nt / lcols / RP / bands / per_xcd / TI / RMAX / nbh / nbw), ``rc`` = 1 where the call itself
+    would be an invalid argument.  ``op`` in UPSAMPLE_OPS; ``n`` = planes (B * C) for the NCHW ops, B for the others;
+    ``pixel_stride`` defaults to C (dense); only the alignment of the two addresses matters.  ``general_only`` /
+    ``xcd_order`` default to the process configuration, which is what the entries pass."""
+    out = (C.c_int32 * len(_UPSAMPLE_PLAN_FIELDS))()
+    L = lib()
+    general_only = L.sea_process_config(1) if general_only is None else int(bool(general_only))
+    xcd_order = L.sea_process_config(0) if xcd_order is None else int(xcd_order)
+    rc = L.sea_upsample_plan(UPSAMPLE_OPS.index(op), n, C_, h, w, H, W, C_ if pixel_stride is None else pixel_stride, src_addr,
+                             dst_addr, general_only, xcd_order, out)
+    plan = dict(zip(_UPSAMPLE_PLAN_FIELDS, out), rc=rc)
+    total = (plan.pop("total_hi") << 32) | (plan.pop("total_lo") & 0xffffffff)
+    return dict(plan, kernel=UPSAMPLE_KERNELS[plan["kernel"]], total=total)
 
 
 # ------------------------------------------------------------------------------------------------ M6
