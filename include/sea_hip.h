@@ -711,6 +711,30 @@ int sea_sw_merge(const float* logits, float* out, int B, int C, int hl, int wl, 
 int sea_sw_finish(const float* avg, float* score, int B, int C, int H, int W, int Ho, int Wo, int flip, int accumulate,
                   void* stream);
 
+/* The attack through the windows (semseg.utils.segmenter_eval.SlidingWindowModel): the cut of the windows and the
+ * adjoints of cut and merge.  Anchors, limits and checks as for sea_sw_merge; all are gathers with one lane per output
+ * element and a fixed summation order: no atomics, bitwise reproducible.
+ * sea_sw_cut (K11c, semseg/utils/segmenter_eval.py:51-67, sliding_window): crops (B * n_h * n_w, Cx, ws, ws), image-major,
+ *   window ih * n_w + iw = x[b, :, h_anchors[ih] .. + ws, w_anchors[iw] .. + ws] of x (B, Cx, H, W): a copy, the bits of
+ *   the stack of slices.
+ * sea_sw_cut_bwd (K11c', the adjoint of segmenter_eval.py:51-67): dx[b, c, y, x] = the fp32 sum, from 0.f, of
+ *   dcrops[b, k, c, y - ha, x - wa] over the windows k that cover (y, x), h anchor outer, w anchor inner.
+ * sea_sw_merge_bwd (K11a', the adjoint of segmenter_eval.py:70-83 = sea_sw_merge with softmax == 0): g (B, C, H, W) is the
+ *   gradient of the averaged logits, dlogits (B * n_h * n_w, C, hl, wl) that of the window logits.
+ *   hl == ws and wl == ws: dlogits[b, k, c, i, j] = g[b, c, ha + i, wa + j] / (float)count(ha + i, wa + j), one correctly
+ *   rounded division (autograd through the reference's logit / count).
+ *   smaller: the adjoint of the in-kernel M2 up-sampling, with the forward's taps and weights, applied to g / count
+ *   restricted to the window; every low-resolution element adds its window pixels row-major (a row's sum, then the rows).
+ *   Neither g / count nor a (B * n_h * n_w, C, ws, ws) gradient is written.  This mode keeps a table of the window's
+ *   columns in LDS (8 bytes per column, padded; at most 48 KB): ws up to about 3000, beyond that hipErrorInvalidValue.
+ *   dlogits must not alias g. */
+int sea_sw_cut(const float* x, float* crops, int B, int Cx, int ws, const int* h_anchors, int n_h, const int* w_anchors,
+               int n_w, int H, int W, void* stream);
+int sea_sw_cut_bwd(const float* dcrops, float* dx, int B, int Cx, int ws, const int* h_anchors, int n_h,
+                   const int* w_anchors, int n_w, int H, int W, void* stream);
+int sea_sw_merge_bwd(const float* g, float* dlogits, int B, int C, int hl, int wl, int ws, const int* h_anchors, int n_h,
+                     const int* w_anchors, int n_w, int H, int W, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * P1-P3: PSPNet-ResNet50 (semseg/models/ddcat_psp.py:372-486 with backbones/resnet_ddcat.py), the steps of its frozen
  * eval forward / input gradient that are not convolutions.  All fp32.

@@ -145,6 +145,9 @@ _SIGS = {
     "sea_sw_merge": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int), _i, _i, _i, _i, _i, _i,
                           _vp]),
     "sea_sw_finish": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "sea_sw_cut": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int), _i, _i, _i, _vp]),
+    "sea_sw_cut_bwd": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int), _i, _i, _i, _vp]),
+    "sea_sw_merge_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int), _i, _i, _i, _vp]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -720,6 +723,72 @@ def sw_finish(avg, out_size, *, flip: bool = False, out=None, accumulate: bool =
     _check(lib().sea_sw_finish(_p(avg), _p(out), B, Cc, H, W, Ho, Wo, int(bool(flip)), int(bool(accumulate)), _stream()),
            "sea_sw_finish")
     return out
+
+
+def _sw_anchor_args(name, h_anchors, w_anchors):
+    ha, wa = [int(a) for a in h_anchors], [int(a) for a in w_anchors]
+    n_h, n_w = len(ha), len(wa)
+    if not (1 <= n_h <= SW_MAX_ANCHORS and 1 <= n_w <= SW_MAX_ANCHORS):
+        raise SeaNativeError(f"{name}: {n_h} x {n_w} anchors, 1 .. {SW_MAX_ANCHORS} per axis are supported")
+    return (C.c_int * n_h)(*ha), n_h, (C.c_int * n_w)(*wa), n_w
+
+
+def sw_cut(x, window_size, h_anchors, w_anchors):
+    """K11c, the windows of ``x`` (B, Cx, H, W) as one (B * n_win, Cx, ws, ws) tensor (reference
+    semseg/utils/segmenter_eval.py:51-67): image-major, window ``ih * n_w + iw`` of an image =
+    ``x[b, :, ha:ha + ws, wa:wa + ws]``; the bits of the stack of slices."""
+    _dev(x)
+    x = _f32c(x)
+    if x.dim() != 4:
+        raise SeaNativeError(f"sw_cut: expected (B, C, H, W), got {tuple(x.shape)}")
+    ha, n_h, wa, n_w = _sw_anchor_args("sw_cut", h_anchors, w_anchors)
+    B, Cx, H, W = x.shape
+    ws = int(window_size)
+    if ws > H or ws > W:
+        raise SeaNativeError(f"sw_cut: window {ws} larger than the image {H}x{W}")
+    crops = torch.empty((B * n_h * n_w, Cx, ws, ws), dtype=torch.float32, device=x.device)
+    _check(lib().sea_sw_cut(_p(x), _p(crops), B, Cx, ws, ha, n_h, wa, n_w, H, W, _stream()), "sea_sw_cut")
+    return crops
+
+
+def sw_cut_backward(dcrops, window_size, h_anchors, w_anchors, size):
+    """K11c', the adjoint of ``sw_cut``: ``dcrops`` (B * n_win, Cx, ws, ws) -> (B, Cx, H, W) with ``size`` = (H, W); per
+    pixel the fp32 sum of the covering windows' gradients in anchor order (h outer, w inner)."""
+    _dev(dcrops)
+    dcrops = _f32c(dcrops)
+    ws, (H, W) = int(window_size), (int(size[0]), int(size[1]))
+    if dcrops.dim() != 4 or dcrops.shape[2] != ws or dcrops.shape[3] != ws:
+        raise SeaNativeError(f"sw_cut_backward: expected (B * n_win, C, {ws}, {ws}), got {tuple(dcrops.shape)}")
+    ha, n_h, wa, n_w = _sw_anchor_args("sw_cut_backward", h_anchors, w_anchors)
+    N_, Cx = dcrops.shape[:2]
+    if N_ % (n_h * n_w):
+        raise SeaNativeError(f"sw_cut_backward: {N_} windows are no multiple of {n_h} x {n_w} windows per image")
+    B = N_ // (n_h * n_w)
+    dx = torch.empty((B, Cx, H, W), dtype=torch.float32, device=dcrops.device)
+    _check(lib().sea_sw_cut_bwd(_p(dcrops), _p(dx), B, Cx, ws, ha, n_h, wa, n_w, H, W, _stream()), "sea_sw_cut_bwd")
+    return dx
+
+
+def sw_merge_backward(g, window_size, h_anchors, w_anchors, logits_size):
+    """K11a', the adjoint of ``sw_merge(softmax=False)``: ``g`` (B, C, H, W), the gradient of the averaged logits ->
+    the gradient of the window logits (B * n_win, C, hl, wl) with ``logits_size`` = (hl, wl).  ``hl == wl == window_size``:
+    ``g[b, c, ha + i, wa + j] / count``; smaller (``forward_lowres`` logits): the adjoint of the in-kernel up-sampling
+    applied to that quotient, which is not written."""
+    _dev(g)
+    g = _f32c(g)
+    if g.dim() != 4:
+        raise SeaNativeError(f"sw_merge_backward: expected (B, C, H, W), got {tuple(g.shape)}")
+    ha, n_h, wa, n_w = _sw_anchor_args("sw_merge_backward", h_anchors, w_anchors)
+    B, Cc, H, W = g.shape
+    ws, (hl, wl) = int(window_size), (int(logits_size[0]), int(logits_size[1]))
+    if Cc > MSF_MAX_CLASSES:
+        raise SeaNativeError(f"sw_merge_backward: {Cc} classes > {MSF_MAX_CLASSES}")
+    if hl > ws or wl > ws or hl < 1 or wl < 1:
+        raise SeaNativeError(f"sw_merge_backward: logits {hl}x{wl} do not fit the window {ws}")
+    dlogits = torch.empty((B * n_h * n_w, Cc, hl, wl), dtype=torch.float32, device=g.device)
+    _check(lib().sea_sw_merge_bwd(_p(g), _p(dlogits), B, Cc, hl, wl, ws, ha, n_h, wa, n_w, H, W, _stream()),
+           "sea_sw_merge_bwd")
+    return dlogits
 
 
 # ------------------------------------------------------------------------------------------------ P1-P3 (PSPNet)

@@ -4,6 +4,8 @@ windows at ``window_stride``, the window logits are averaged where they overlap,
 into probabilities.  ``padding``, ``unpadding``, ``resize`` and ``sliding_window`` follow the reference's rules; the
 merge runs in libsea_hip's K11 kernels (``_native.sw_merge`` / ``sw_finish``) as a gather: no sum, count, quotient or
 resized copy of the logits is written, and with a ``forward_lowres`` model not even the full-resolution window logits.
+``SlidingWindowModel`` is the same protocol as a differentiable module (window cut K11c, merge K11a, their adjoints K11c'
+and K11a'), so that the attacks of ``semseg.attacker`` run on whole images.
 """
 from __future__ import annotations
 
@@ -13,7 +15,8 @@ import torch.nn.functional as F
 from .. import _native as N
 from ..attacker import _FrozenParameters
 
-__all__ = ["padding", "unpadding", "resize", "sliding_window", "sw_anchors", "merge_windows", "inference"]
+__all__ = ["padding", "unpadding", "resize", "sliding_window", "sw_anchors", "merge_windows", "inference",
+           "SlidingWindowModel"]
 
 
 def padding(im, patch_size, fill_value=0):
@@ -175,3 +178,91 @@ def inference(model, ims, window_size, window_stride, batch_size, ori_shape=None
                     seg_maps = torch.empty((n_rows, *logits.shape[1:]), dtype=torch.float32, device=logits.device)
                 seg_maps[i:i + step] = logits
     return _merge(seg_maps, ws, h_anchors, w_anchors, (H, W), ori_shape, bool(flip), out=out, accumulate=accumulate)
+
+
+class _SwCut(torch.autograd.Function):
+    """K11c forward, K11c' backward"""
+
+    @staticmethod
+    def forward(ctx, x, ws, h_anchors, w_anchors):
+        ctx.args = (ws, h_anchors, w_anchors, tuple(x.shape[2:]))
+        return N.sw_cut(x, ws, h_anchors, w_anchors)
+
+    @staticmethod
+    def backward(ctx, dcrops):
+        ws, h_anchors, w_anchors, size = ctx.args
+        return N.sw_cut_backward(dcrops.contiguous(), ws, h_anchors, w_anchors, size), None, None, None
+
+
+class _SwMerge(torch.autograd.Function):
+    """K11a (averaged logits) forward, K11a' backward"""
+
+    @staticmethod
+    def forward(ctx, logits, ws, h_anchors, w_anchors, size):
+        ctx.args = (ws, h_anchors, w_anchors, tuple(logits.shape[2:]))
+        return N.sw_merge(logits, ws, h_anchors, w_anchors, size)
+
+    @staticmethod
+    def backward(ctx, g):
+        ws, h_anchors, w_anchors, logits_size = ctx.args
+        return N.sw_merge_backward(g.contiguous(), ws, h_anchors, w_anchors, logits_size), None, None, None, None
+
+
+class SlidingWindowModel(torch.nn.Module):
+    """``model`` evaluated through sliding windows, as a model: (B, 3, H, W) -> the overlap-averaged LOGITS (B, C, H, W) of
+    ``merge_windows`` (whose probabilities are their softmax), differentiable with respect to the input.  The attacks
+    (``apgd_train``, ``apgd_largereps``) take it like any other model and then attack the protocol that
+    ``inference`` / ``evaluate_sliding`` score.
+
+    1. cut the windows of all B images (K11c); 2. window logits ``batch_size`` windows at a time (default: all at once),
+    from ``model.forward_lowres`` when the model offers it; 3. merge (K11a), the model's final up-sampling inside for
+    low-resolution logits.  The backward runs the adjoints K11a' and K11c'.  An image that is exactly one window is the
+    model itself: ``model(x)`` is returned.  There is no resizing (the attack's labels have the image's size): an image
+    smaller than the window is a ValueError.  Nothing is read by the host, so the forward can be captured in a HIP graph.
+    The wrapper deliberately has no ``forward_lowres``: its logits are full resolution.  ``training`` is the inner
+    model's flag."""
+
+    def __init__(self, model, window_size, window_stride, batch_size=None):
+        super().__init__()
+        ws, st = int(window_size), int(window_stride)
+        if ws < 1 or st < 1:
+            raise ValueError(f"window_size {ws} and window_stride {st} must be positive")
+        if st > ws:
+            raise ValueError(f"window_stride {st} > window_size {ws} leaves pixels uncovered")
+        if batch_size is not None and int(batch_size) < 1:
+            raise ValueError(f"batch_size {batch_size} must be positive")
+        if not isinstance(model, torch.nn.Module):
+            raise TypeError("SlidingWindowModel wraps an nn.Module")
+        self.model = model
+        self.window_size, self.window_stride = ws, st
+        self.batch_size = None if batch_size is None else int(batch_size)
+
+    # ``training`` is not a flag of the wrapper's own: it reads the inner model's, and assigning to it (nn.Module.__init__,
+    # train(), or a caller setting ``wrapper.training`` alone) changes nothing.  train() / eval() still reach the inner model,
+    # because nn.Module.train() recurses into the children.
+    @property
+    def training(self):
+        inner = self.__dict__.get("_modules", {}).get("model")
+        return True if inner is None else inner.training
+
+    @training.setter
+    def training(self, mode):
+        pass
+
+    def forward(self, x):
+        if x.dim() != 4:
+            raise ValueError(f"SlidingWindowModel: expected (B, 3, H, W) images, got {tuple(x.shape)}")
+        B, _, H, W = x.shape
+        ws = self.window_size
+        h_anchors, w_anchors = sw_anchors(H, W, ws, self.window_stride)      # ValueError for an image below the window
+        n_win = len(h_anchors) * len(w_anchors)
+        if n_win == 1:
+            return self.model(x)
+        crops = _SwCut.apply(x.float().contiguous(), ws, h_anchors, w_anchors)
+        n_rows = B * n_win
+        step = n_rows if self.batch_size is None else self.batch_size
+        if step >= n_rows:
+            logits = _window_logits(self.model, crops)
+        else:
+            logits = torch.cat([_window_logits(self.model, crops[i:i + step]) for i in range(0, n_rows, step)])
+        return _SwMerge.apply(logits, ws, h_anchors, w_anchors, (H, W))

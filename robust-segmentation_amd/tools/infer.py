@@ -242,7 +242,15 @@ def _main(argv=None):
     ap.add_argument("--dump_stats", type=str, default=None, help="save the all-reduced packed statistics buffer (rank 0)")
     ap.add_argument("--deterministic", action="store_true",
                     help="no MIOpen find-mode benchmarking (its timing-based algorithm choice differs between processes)")
+    ap.add_argument("--window", type=int, default=None,
+                    help="evaluate and attack through sliding windows of this size (semseg.utils.segmenter_eval."
+                         "SlidingWindowModel): the protocol of tools/eval_sliding.py, for images larger than the window")
+    ap.add_argument("--stride", type=int, default=None, help="with --window: the window stride (default: the window)")
+    ap.add_argument("--window_batch", type=int, default=None,
+                    help="with --window: windows per model call (default: all windows of a batch at once)")
     args = ap.parse_args(argv)
+    if args.window is None and (args.stride is not None or args.window_batch is not None):
+        ap.error("--stride and --window_batch need --window")
 
     with open(args.cfg) as f:
         cfg = yaml.load(f, Loader=yaml.SafeLoader)
@@ -288,6 +296,10 @@ def _main(argv=None):
         frac = balance_classes(model, images)          # every rank fits the same bias on the same full image set
         if rank == 0:
             print(f"[infer] balanced classes: min / max pixel share {float(frac.min()):.4f} / {float(frac.max()):.4f}")
+    if args.window is not None:
+        # clean pass, attacks and the adversarial predictions all see the overlap-averaged logits of the windows
+        from semseg.utils.segmenter_eval import SlidingWindowModel
+        model = SlidingWindowModel(model, args.window, args.stride or args.window, args.window_batch)
     if args.n_batches > 0:
         n_img = min(n_img, args.n_batches * bs * world)
     mine = shard_indices(n_img, rank, world)
