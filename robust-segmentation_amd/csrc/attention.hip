@@ -19,43 +19,13 @@
 // Operand maps of v_mfma_f32_32x32x2_f32: A[i = lane&31][k = lane>>5], B[k = lane>>5][j = lane&31],
 // C/D[i = (reg&3) + 8*(reg>>2) + 4*(lane>>5)][j = lane&31].  The head dimension (64) is walked as d = 32*h + s for
 // step s of lane-half h, so that a lane's 32 operand values are contiguous in memory / LDS (8 x 16-byte reads).
-#include "sea_common.h"
+#include "attention_common.h"
 
 namespace sea {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kD = 64;        // head dimension (ViT-S/16: 384 / 6; mask transformer: 384 / 6)
-constexpr int kTile = 64;     // keys (or queries) per LDS tile
 constexpr int kRow = kD + 4;  // LDS row stride in floats: 16-byte reads of 16 different rows hit 16 different bank slots
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
 
-__device__ __forceinline__ int acc_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
-
-// v_exp_f32 itself (2^x, flushes results below 2^-126 to zero: irrelevant next to a soft-max sum >= 1)
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.f;
-  return z;
-}
-
-// 64 rows x 64 floats of a (row-strided) matrix -> LDS tile [64][kRow]; rows >= n_valid are clamped to the last valid
-// row (their results are masked or never stored).  256 threads, 4 float4 per thread.
-__device__ __forceinline__ void load_tile_regs(const float* __restrict__ base, int64_t row_stride, int row0, int n_rows,
-                                               f32x4 (&r)[4]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int e = (int)threadIdx.x + 256 * i;  // float4 index in the tile
-    int row = row0 + (e >> 4);
-    row = row < n_rows ? row : n_rows - 1;
-    r[i] = *reinterpret_cast<const f32x4*>(base + (int64_t)row * row_stride + 4 * (e & 15));
-  }
-}
+// registers of load_tile_regs -> LDS tile [64][kRow].  256 threads, 4 float4 per thread.
 __device__ __forceinline__ void store_tile_lds(float* __restrict__ tile, const f32x4 (&r)[4]) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -103,32 +73,6 @@ __device__ __forceinline__ f32x16 tile_t_times_acc(const float* __restrict__ til
   }
   return acc;
 }
-
-// store a transposed accumulator pair (d-tile 0 and 1) of 32 rows: out[row0 + (lane&31)][d], 16-byte stores
-__device__ __forceinline__ void store_rows_t(float* __restrict__ base, int64_t row_stride, int row, bool ok, int lane,
-                                             const f32x16& t0, const f32x16& t1, float mul) {
-  if (!ok) return;
-  const int half = lane >> 5;
-  float* p = base + (int64_t)row * row_stride;
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    f32x4 a, b;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      a[k] = t0[4 * g + k] * mul;
-      b[k] = t1[4 * g + k] * mul;
-    }
-    *reinterpret_cast<f32x4*>(p + 8 * g + 4 * half) = a;
-    *reinterpret_cast<f32x4*>(p + 32 + 8 * g + 4 * half) = b;
-  }
-}
-
-struct AttnPtrs {
-  const float* q;  // element (b, h, t, d) at q + b*sb + h*sh + t*st + d   (same strides for k and v)
-  const float* k;
-  const float* v;
-  int64_t sb, sh, st;
-};
 
 // ---- forward ---------------------------------------------------------------------------------------------------------
 // grid (ceil(T / 128), H, B), block 256: wave w owns query rows [128*bx + 32*w, +32).
@@ -354,40 +298,25 @@ __global__ __launch_bounds__(256, 2) void attn_dkv_kernel(AttnPtrs p, int T, int
 
 using namespace sea;
 
-// M7b (csrc/attention_bf16.hip): the same three kernels on the bf16 matrix cores by operand splitting.
-int sea_attention_fwd_bf16(const float* q, const float* k, const float* v, int64_t sb, int64_t sh, int64_t st, int B, int H, int T,
-                           float scale, float* out, float* lse, int terms, hipStream_t stream);
-int sea_attention_bwd_bf16(const float* q, const float* k, const float* v, int64_t sb, int64_t sh, int64_t st, int B, int H, int T,
-                           float scale, const float* grad_out, const float* lse, const float* delta, float* dq, float* dk,
-                           float* dv, int64_t gsb, int64_t gsh, int64_t gst, int terms, hipStream_t stream);
-
-int sea_attention_bwd_f16x2(const float* q, const float* k, const float* v, int64_t sb, int64_t sh, int64_t st, int B, int H, int T,
-                            float scale, const float* grad_out, const float* lse, const float* delta, uint32_t* amax_ws, float* dq,
-                            float* dk, float* dv, int64_t gsb, int64_t gsh, int64_t gst, hipStream_t stream);
-
-int sea_attention_fwd_f16x2(const float* q, const float* k, const float* v, int64_t sb, int64_t sh, int64_t st, int B, int H, int T,
-                            float scale, uint32_t* amax_ws, float* out, float* lse, hipStream_t stream);
+static int attention_fwd_impl(const float* q, const float* k, const float* v, int64_t sb, int64_t sh, int64_t st, int B, int H,
+                              int T, int D, float scale, float* out, float* lse, int arith, void* stream,
+                              uint32_t* amax_ws = nullptr) {
+  SEA_CHECK_ARG(q && k && v && out && lse && B > 0 && H > 0 && T > 0 && D == kD);
+  SEA_CHECK_ARG((sb % 4) == 0 && (sh % 4) == 0 && (st % 4) == 0 &&
+                ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)out)) & 15) == 0);
+  AttnPtrs p{q, k, v, sb, sh, st};
+  if (arith)
+    return sea_attention_fwd_split(p, B, H, T, scale, out, lse, arith, amax_ws, (hipStream_t)stream);
+  dim3 grid((T + 127) / 128, H, B), block(256);
+  hipLaunchKernelGGL(attn_fwd_kernel, grid, block, 0, (hipStream_t)stream, p, T, H, scale, out, lse);
+  SEA_RETURN_LAST();
+}
 
 // the forward with fp16 x 2 operands (22 significant bits, three MFMA products per pair); amax_ws: 4 B H words of scratch
 extern "C" int sea_attention_fwd_f16(const float* q, const float* k, const float* v, int64_t sb, int64_t sh, int64_t st, int B, int H,
                                      int T, int D, float scale, uint32_t* amax_ws, float* out, float* lse, void* stream) {
-  SEA_CHECK_ARG(q && k && v && out && lse && amax_ws && B > 0 && H > 0 && T > 0 && D == kD);
-  SEA_CHECK_ARG((sb % 4) == 0 && (sh % 4) == 0 && (st % 4) == 0 &&
-                ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)out)) & 15) == 0);
-  return sea_attention_fwd_f16x2(q, k, v, sb, sh, st, B, H, T, scale, amax_ws, out, lse, (hipStream_t)stream);
-}
-
-static int attention_fwd_impl(const float* q, const float* k, const float* v, int64_t sb, int64_t sh, int64_t st, int B, int H,
-                              int T, int D, float scale, float* out, float* lse, int terms, void* stream) {
-  SEA_CHECK_ARG(q && k && v && out && lse && B > 0 && H > 0 && T > 0 && D == kD);
-  SEA_CHECK_ARG((sb % 4) == 0 && (sh % 4) == 0 && (st % 4) == 0 &&
-                ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v) | ((uintptr_t)out)) & 15) == 0);
-  if (terms)
-    return sea_attention_fwd_bf16(q, k, v, sb, sh, st, B, H, T, scale, out, lse, terms, (hipStream_t)stream);
-  AttnPtrs p{q, k, v, sb, sh, st};
-  dim3 grid((T + 127) / 128, H, B), block(256);
-  hipLaunchKernelGGL(attn_fwd_kernel, grid, block, 0, (hipStream_t)stream, p, T, H, scale, out, lse);
-  SEA_RETURN_LAST();
+  SEA_CHECK_ARG(amax_ws != nullptr);
+  return attention_fwd_impl(q, k, v, sb, sh, st, B, H, T, D, scale, out, lse, 22, stream, amax_ws);
 }
 
 // q/k/v: element (b,h,t,d) at ptr + b*sb + h*sh + t*st + d (floats), d contiguous, head dim 64, 16-byte aligned rows;
@@ -437,10 +366,8 @@ static int attention_bwd_impl(const float* q, const float* k, const float* v, in
   hipStream_t s = (hipStream_t)stream;
   const int64_t rows = (int64_t)B * T * H;
   hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, s, out, grad_out, T, H, rows, delta);
-  if (bwd_terms == 22)
-    return sea_attention_bwd_f16x2(q, k, v, sb, sh, st, B, H, T, scale, grad_out, lse, delta, amax_ws, dq, dk, dv, gsb, gsh, gst, s);
-  if (const int terms = bwd_terms)
-    return sea_attention_bwd_bf16(q, k, v, sb, sh, st, B, H, T, scale, grad_out, lse, delta, dq, dk, dv, gsb, gsh, gst, terms, s);
+  if (bwd_terms)
+    return sea_attention_bwd_split(p, B, H, T, scale, grad_out, lse, delta, dq, dk, dv, gsb, gsh, gst, bwd_terms, amax_ws, s);
   dim3 grid((T + 127) / 128, H, B), block(256);
   hipLaunchKernelGGL(attn_dq_kernel, grid, block, 0, s, p, T, H, scale, grad_out, lse, delta, dq, gsb, gsh, gst);
   hipLaunchKernelGGL(attn_dkv_kernel, grid, block, 0, s, p, T, H, scale, grad_out, lse, delta, dk, dv, gsb, gsh, gst);

@@ -1146,7 +1146,9 @@ def test_counts_full_size_ade(N):
 
 # ------------------------------------------------------------------------------------------------ M7 attention
 @pytest.mark.parametrize("case", [(2, 6, 1025, "ViT-S/16 encoder, 512x512"), (1, 6, 1175, "mask transformer, 1024 patches + 151 classes"),
-                                  (3, 2, 64, "one tile"), (1, 1, 33, "ragged"), (2, 3, 130, "two blocks, ragged")])
+                                  (3, 2, 64, "one tile"), (1, 1, 33, "ragged"), (2, 3, 130, "two blocks, ragged"),
+                                  (2, 2, 1, "one row, every other lane clamped"), (2, 2, 65, "second tile with one key"),
+                                  (2, 2, 129, "second block with one row, three idle waves")])
 @pytest.mark.parametrize("terms", [(22, 22), (3, 22), (3, 2), (3, 3), (0, 0)])
 def test_fp32_mfma_attention_forward_and_backward(N, case, terms):
     """softmax(q k^T * scale) v as written in the reference (vit_encoder.py:106-127), explicit fp32 (and an fp64 check).
