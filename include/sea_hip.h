@@ -897,6 +897,30 @@ int sea_train_ce_up_pow2_fwd(const float* low, const int64_t* y, const float* wg
                              void* stream);
 int sea_train_ce_up_pow2_scale(const double* raw, const float* g, const void* words, float* dlow, int64_t n, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The attack through multi-scale + flip (semseg.utils.msf_model.MsfModel): the adjoints of K10 (csrc/msf_grad.hip).
+ * Gathers with one lane per output element and a fixed summation order: no atomics, bitwise reproducible.  Every index
+ * and weight is the forward's (the same device functions).
+ * sea_msf_resize_bwd (K10r', the adjoint of sea_msf_resize_input = of the interpolate(images, align_corners=True)
+ *   [+ flip] of semseg/val.py:340-365): g and / or g_flip (planes, H, W), the gradients of y and y_flip, -> dsrc
+ *   (planes, h, w), the gradient of x.  Either may be NULL, not both.  Per source element, fp32 from 0.f:
+ *   acc += (wy * wx) * g[p, Y, X] over the destination pixels (Y, X) whose forward map references it, Y ascending, then
+ *   X ascending, row tap 0 before row tap 1, column tap 0 before column tap 1 (a clamped border pixel contributes both
+ *   of its terms); all terms of g first, then those of g_flip (read at column W-1-X) in the same order.  An element
+ *   that no destination references gets 0.  src_flip != 0: the mirror is on the SOURCE columns instead (element
+ *   (i, c) collects the terms of map column w-1-c), as in sea_msf_accumulate with flip.  Up or down.  h*w and
+ *   H*W < 2^31.  dsrc must alias neither gradient.
+ * sea_msf_accumulate_bwd (K10g + K10r', the adjoint of sea_msf_accumulate with respect to the logits): dscore
+ *   (B, C, H, W) is the gradient of score.  K10g recomputes per pixel the resized logits v and p = softmax(v) exactly
+ *   as sea_msf_accumulate (both modes, flip) and writes G = p * (dscore - sum_c p_c dscore_c) into the workspace G
+ *   (B, C, H, W); K10r' (src_flip = flip) then writes dscaled (B, C, Hs, Ws), the gradient on the scaled grid.  hl == Hs
+ *   and wl == Ws: dscaled is the gradient of the logits.  Smaller (forward_lowres logits): the caller follows with
+ *   sea_upsample_bilinear_bwd down to (hl, wl).  Limits as sea_msf_accumulate; the four buffers must not alias. */
+int sea_msf_resize_bwd(const float* g, const float* g_flip, float* dsrc, int64_t planes, int h, int w, int H, int W,
+                       int src_flip, void* stream);
+int sea_msf_accumulate_bwd(const float* logits, const float* dscore, float* G, float* dscaled, int B, int C, int hl,
+                           int wl, int Hs, int Ws, int H, int W, int flip, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,7 @@ SOURCES = [
     ("mlp_fused.hip", ["-fno-slp-vectorize"]),
     ("classifier.hip", []),
     ("msf_kernels.hip", ["-ffp-contract=off"]),
+    ("msf_grad.hip", ["-ffp-contract=off"]),
     ("sw_kernels.hip", ["-ffp-contract=off"]),
     ("psp_kernels.hip", []),
     ("bn_train.hip", []),
@@ -59,7 +60,7 @@ SOURCES = [
     ("greedy_host.cpp", ["-ffp-contract=off"]),
     ("api_misc.cpp", []),
 ]
-HEADERS = ["sea_common.h", "attention_common.h", "colsum.h", "loss_common.h", "loss_plan.h", "gemm_plan.h", "upsample_plan.h", "launch_grid.h", "gemm_split.h", "bilinear_map.h", "train_loss_common.h", os.path.join("..", "..", "include", "sea_hip.h")]
+HEADERS = ["sea_common.h", "attention_common.h", "colsum.h", "loss_common.h", "loss_plan.h", "gemm_plan.h", "upsample_plan.h", "launch_grid.h", "gemm_split.h", "bilinear_map.h", "msf_map.h", "train_loss_common.h", os.path.join("..", "..", "include", "sea_hip.h")]
 
 
 def _hipcc() -> str:

@@ -148,6 +148,8 @@ _SIGS = {
     "sea_sw_cut": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int), _i, _i, _i, _vp]),
     "sea_sw_cut_bwd": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int), _i, _i, _i, _vp]),
     "sea_sw_merge_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int), _i, _i, _i, _vp]),
+    "sea_msf_resize_bwd": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp]),
+    "sea_msf_accumulate_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -654,6 +656,58 @@ def msf_accumulate(logits, score, scaled_size, flip: bool = False):
     _check(lib().sea_msf_accumulate(_p(logits), _p(score), B, Cc, hl, wl, Hs, Ws, H, W, int(bool(flip)), _stream()),
            "sea_msf_accumulate")
     return score
+
+
+def msf_resize_input_backward(g, g_flip, in_size):
+    """K10a', the adjoint of ``msf_resize_input``: ``g`` / ``g_flip`` (B, C, H, W), the gradients of the plain and of the
+    mirrored scaled image (either may be None), -> the gradient (B, C, h, w) of the input with ``in_size`` = (h, w).  One
+    launch, a gather in a fixed order (plain terms first, then the mirrored ones): bitwise reproducible."""
+    _dev(g, g_flip)
+    ref = g if g is not None else g_flip
+    if ref is None:
+        raise SeaNativeError("msf_resize_input_backward: no gradient given")
+    for t in (g, g_flip):
+        if t is not None and (_f32c(t).dim() != 4 or t.shape != ref.shape):
+            raise SeaNativeError(f"msf_resize_input_backward: expected (B, C, H, W) gradients of one shape, got "
+                                 f"{tuple(t.shape)} and {tuple(ref.shape)}")
+    B, Cc, H, W = ref.shape
+    h, w = int(in_size[0]), int(in_size[1])
+    if h <= 0 or w <= 0:
+        raise SeaNativeError(f"msf_resize_input_backward: input size {h}x{w}")
+    dx = torch.empty((B, Cc, h, w), dtype=torch.float32, device=ref.device)
+    _check(lib().sea_msf_resize_bwd(_p(g), _p(g_flip), _p(dx), B * Cc, h, w, H, W, 0, _stream()), "sea_msf_resize_bwd")
+    return dx
+
+
+def msf_accumulate_backward(logits, dscore, scaled_size, flip: bool = False, workspace=None):
+    """The adjoint of ``msf_accumulate`` with respect to ``logits``: ``dscore`` (B, C, H, W), the gradient of the score
+    buffer, -> the gradient in ``logits``' shape.  K10g (softmax backward at label resolution, the resized logits recomputed
+    as in the forward) writes ``workspace`` (B, C, H, W; allocated here when None), K10r' gathers it onto the scaled grid
+    and, for ``forward_lowres`` logits, M2's backward (``upsample_bilinear_backward``) takes it down to their size."""
+    _dev(logits, dscore, workspace)
+    logits, dscore = _f32c(logits), _f32c(dscore)
+    if logits.dim() != 4 or dscore.dim() != 4:
+        raise SeaNativeError("msf_accumulate_backward: logits and dscore must be (B, C, h, w) / (B, C, H, W)")
+    B, Cc, hl, wl = logits.shape
+    Hs, Ws = int(scaled_size[0]), int(scaled_size[1])
+    if dscore.shape[0] != B or dscore.shape[1] != Cc:
+        raise SeaNativeError(f"msf_accumulate_backward: dscore {tuple(dscore.shape)} does not match logits "
+                             f"{tuple(logits.shape)}")
+    if Cc > MSF_MAX_CLASSES:
+        raise SeaNativeError(f"msf_accumulate_backward: {Cc} classes > {MSF_MAX_CLASSES}")
+    if hl > Hs or wl > Ws:
+        raise SeaNativeError(f"msf_accumulate_backward: logits {hl}x{wl} larger than the scaled size {Hs}x{Ws}")
+    H, W = dscore.shape[2:]
+    if workspace is None:
+        workspace = torch.empty_like(dscore)
+    elif tuple(workspace.shape) != tuple(dscore.shape):
+        raise SeaNativeError(f"msf_accumulate_backward: workspace {tuple(workspace.shape)} != {tuple(dscore.shape)}")
+    dscaled = torch.empty((B, Cc, Hs, Ws), dtype=torch.float32, device=logits.device)
+    _check(lib().sea_msf_accumulate_bwd(_p(logits), _p(dscore), _p(_f32c(workspace)), _p(dscaled), B, Cc, hl, wl, Hs, Ws, H, W,
+                                        int(bool(flip)), _stream()), "sea_msf_accumulate_bwd")
+    if hl == Hs and wl == Ws:
+        return dscaled
+    return upsample_bilinear_backward(dscaled, (hl, wl))
 
 
 # ------------------------------------------------------------------------------------------------ K11

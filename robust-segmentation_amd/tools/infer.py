@@ -248,9 +248,25 @@ def _main(argv=None):
     ap.add_argument("--stride", type=int, default=None, help="with --window: the window stride (default: the window)")
     ap.add_argument("--window_batch", type=int, default=None,
                     help="with --window: windows per model call (default: all windows of a batch at once)")
+    ap.add_argument("--msf-scales", dest="msf_scales", type=str, default=None,
+                    help="evaluate and attack the multi-scale ensemble of semseg.val.evaluate_msf (semseg.utils.msf_model."
+                         "MsfModel): comma-separated scales, e.g. 0.5,0.75,1.0,1.25,1.5,1.75")
+    ap.add_argument("--msf-flip", dest="msf_flip", action="store_true",
+                    help="with --msf-scales: every scale also on the mirrored image")
     args = ap.parse_args(argv)
     if args.window is None and (args.stride is not None or args.window_batch is not None):
         ap.error("--stride and --window_batch need --window")
+    if args.msf_flip and args.msf_scales is None:
+        ap.error("--msf-flip needs --msf-scales")
+    if args.msf_scales is not None:
+        if args.window is not None:
+            ap.error("--msf-scales and --window are mutually exclusive")
+        try:
+            args.msf_scales = [float(s) for s in args.msf_scales.split(",") if s.strip()]
+        except ValueError:
+            ap.error("--msf-scales: comma-separated numbers expected")
+        if not args.msf_scales or min(args.msf_scales) <= 0:
+            ap.error("--msf-scales: at least one scale, all positive")
 
     with open(args.cfg) as f:
         cfg = yaml.load(f, Loader=yaml.SafeLoader)
@@ -300,6 +316,10 @@ def _main(argv=None):
         # clean pass, attacks and the adversarial predictions all see the overlap-averaged logits of the windows
         from semseg.utils.segmenter_eval import SlidingWindowModel
         model = SlidingWindowModel(model, args.window, args.stride or args.window, args.window_batch)
+    if args.msf_scales is not None:
+        # clean pass, attacks and the adversarial predictions all see the log of the ensemble's score buffer
+        from semseg.utils.msf_model import MsfModel
+        model = MsfModel(model, args.msf_scales, args.msf_flip, n_classes=C)
     if args.n_batches > 0:
         n_img = min(n_img, args.n_batches * bs * world)
     mine = shard_indices(n_img, rank, world)
