@@ -3,12 +3,23 @@
 PyTorch-ROCm forward / backward of the same module (pspnet.USE_NATIVE = False):
 
     python devtools/psp_bench.py [--batch 8] [--size 473] [--classes 21] [--steps 10] [--warmup 3] [--graph 1]
+                                 [--clean 1] [--stem fused] [--windows 0]
 
 Prints one JSON line per mode, with the model-side roofline line: about 0.3 TFLOP per 473 x 473 image for the forward
-(cls 3x3 0.14, layer4 0.10, layer3 0.05) and about the same again for the input gradient."""
+(cls 3x3 0.14, layer4 0.10, layer3 0.05) and about the same again for the input gradient.
+
+``--clean 0`` builds ``PSPNet(clean=False)``, the robust 7x7 stem; ``--stem fused | library`` sets ``pspnet.STEM_FUSED`` for
+the ``native`` mode (P4, csrc/psp_stem.hip, or the library line).  ``--windows N`` (N >= 1) is the A/B form for that model:
+the configurations -- ``native`` with the fused stem, ``native`` with the library stem, ``stock`` -- each get a copy of the
+model and their own attack run, and alternate inside one process: N windows each of ``--steps`` attack steps between two
+device events, median / fastest / slowest window; then the stem alone (forward + input gradient of ``layer0``, fused and
+library alternating, N windows of ``--stem-iters`` passes) with the peak allocation of one pass above the inputs.  A ``#``
+header line, then one JSON line per part."""
 import argparse
+import copy
 import json
 import os
+import statistics
 import sys
 import time
 
@@ -43,6 +54,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--graph", type=int, default=1)
     ap.add_argument("--modes", type=str, default="native,stock")
+    ap.add_argument("--clean", type=int, default=1, choices=(0, 1))
+    ap.add_argument("--stem", type=str, default="fused", choices=("fused", "library"))
+    ap.add_argument("--windows", type=int, default=0)
+    ap.add_argument("--stem-iters", type=int, default=20)
     args = ap.parse_args()
 
     from semseg import attacker as A
@@ -50,9 +65,10 @@ def main():
     from semseg.utils.utils import VOC_WTS
 
     B, S, C = args.batch, args.size, args.classes
-    flops = _flops_per_image(PSPNet(50, C).eval(), S)
+    clean = bool(args.clean)
+    flops = _flops_per_image(PSPNet(50, C, clean=clean).eval(), S)
     torch.manual_seed(0)
-    model = PSPNet(50, C).eval().cuda()
+    model = PSPNet(50, C, clean=clean).eval().cuda()
     for p in model.parameters():
         p.requires_grad_(False)
     x = torch.rand(B, 3, S, S, generator=torch.Generator().manual_seed(1)).cuda()
@@ -60,6 +76,10 @@ def main():
         y = model(x).max(1)[1]
     w = torch.tensor(VOC_WTS, device="cuda")[:C] if C == 21 else torch.ones(C, device="cuda")
     A.USE_HIP_GRAPH = bool(args.graph)
+    if args.windows > 0:
+        assert not clean, "--windows is the A/B of the clean=False stem"
+        return _ab(args, model, x, y, w, flops)
+    pspnet.STEM_FUSED = args.stem == "fused"
     for mode in args.modes.split(","):
         pspnet.USE_NATIVE = mode == "native"
         A.release_graph_cache(model)
@@ -76,11 +96,111 @@ def main():
         torch.cuda.synchronize()
         ms = (time.perf_counter() - t0) * 1e3 / K
         tflops = 2 * flops * B / (ms * 1e-3) / 1e12      # forward + input gradient
-        print(json.dumps({"model": "PSPNet_RN50", "mode": mode, "B": B, "size": S, "classes": C, "graph": bool(args.graph),
+        print(json.dumps({"model": "PSPNet_RN50", "mode": mode, "clean": clean, "stem": args.stem, "B": B, "size": S,
+                          "classes": C, "graph": bool(args.graph),
                           "ms_per_step": round(ms, 3), "fwd_tflop_per_image": round(flops / 1e12, 4),
                           "model_tflops": round(tflops, 1)}), flush=True)
     pspnet.USE_NATIVE = True
     A.release_graph_cache(model)
+
+
+def _summary(ts):
+    return dict(median_ms=round(statistics.median(ts), 4), min_ms=round(min(ts), 4), max_ms=round(max(ts), 4))
+
+
+def _ab(args, model, x, y, w, flops):
+    from semseg import _native as N
+    from semseg import attacker as A
+    from semseg.models import pspnet
+    from semseg.models.convnext_upernet import _folded_bn
+    B, S, C, K, W, NW = args.batch, args.size, args.classes, args.steps, max(args.warmup, 3), args.windows
+    print(f"# devtools/psp_bench.py --clean 0 --windows {NW}: PSPNet(50, {C}, clean=False), random weights, B = {B}, {S}^2, "
+          f"fp32, graph = {bool(args.graph)}; ms per APGD step (mask-ce-bal, Linf), median / fastest / slowest of {NW} windows "
+          f"of {K} steps, the configurations alternating in one process (a model copy and an attack run each); stem: ms per "
+          f"forward + input gradient of layer0 alone, {NW} alternating windows of {args.stem_iters}; peak_MB: "
+          "max_memory_allocated of one pass above the inputs", flush=True)
+    configs = {"fused": (True, True), "library": (True, False), "stock": (False, False)}
+
+    def switch(name):
+        pspnet.USE_NATIVE, pspnet.STEM_FUSED = configs[name]
+
+    runs = {}
+    for name in configs:
+        switch(name)
+        m = copy.deepcopy(model)
+        run = A.ApgdRun(m, x, y, 8.0 / 255, max(W + NW * K + 1, A.GRAPH_MIN_ITER), "mask-ce-bal", "ce-avg", True, C, w,
+                        x.clone())
+        run.start()
+        for i in range(W):
+            run.step(i)
+        runs[name] = (m, run)
+    times = {name: [] for name in configs}
+    for k in range(NW):
+        for name, (m, run) in runs.items():
+            switch(name)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for i in range(W + k * K, W + (k + 1) * K):
+                run.step(i)
+            e1.record()
+            torch.cuda.synchronize()
+            times[name].append(e0.elapsed_time(e1) / K)
+    row = dict(part="apgd_step", model="PSPNet_RN50", clean=False, B=B, size=S, classes=C, graph=bool(args.graph), windows=NW,
+               steps=K, fwd_tflop_per_image=round(flops / 1e12, 4))
+    for name in configs:
+        row[name] = _summary(times[name])
+    row["library_over_fused"] = round(row["library"]["median_ms"] / row["fused"]["median_ms"], 4)
+    print(json.dumps(row), flush=True)
+    for m, run in runs.values():
+        A.release_graph_cache(m)
+    runs.clear()
+
+    # the stem alone
+    l0 = model.layer0
+    scale, shift = _folded_bn(l0[1], l0[0].bias, {})
+    xi = x.clone().requires_grad_(True)
+    Hp, Wp = N.psp_stem_size(S, S)
+    g = torch.randn(B, Hp, Wp, 64, device="cuda", generator=torch.Generator(device="cuda").manual_seed(2)).permute(0, 3, 1, 2)
+    fns = {"fused": lambda: pspnet._RobustStem.apply(xi, l0[0].weight, scale, shift),
+           "library": lambda: l0[3](torch.relu(l0[1](l0[0](xi.contiguous(memory_format=torch.channels_last)))))}
+
+    def one(fn):
+        (gx,) = torch.autograd.grad(fn(), [xi], g)
+        return gx
+
+    def window(fn, iters):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(iters):
+            one(fn)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / iters
+
+    def peak_of(fn):
+        torch.cuda.synchronize()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        one(fn)
+        torch.cuda.synchronize()
+        return torch.cuda.max_memory_allocated() - base
+
+    for name in fns:
+        window(fns[name], 3)
+    stem = {name: [] for name in fns}
+    for _ in range(NW):
+        for name in fns:
+            stem[name].append(window(fns[name], args.stem_iters))
+    row = dict(part="stem", B=B, size=S, out=[Hp, Wp], windows=NW, iters=args.stem_iters,
+               grad_rel_l2_fused_vs_library=round(((one(fns["fused"]) - one(fns["library"])).norm()
+                                                   / one(fns["library"]).norm()).item(), 8))
+    for name in fns:
+        row[name] = dict(_summary(stem[name]), peak_MB=round(peak_of(fns[name]) / 2 ** 20, 1))
+    row["library_over_fused"] = round(row["library"]["median_ms"] / row["fused"]["median_ms"], 4)
+    print(json.dumps(row), flush=True)
+    pspnet.USE_NATIVE, pspnet.STEM_FUSED = True, True
 
 
 if __name__ == "__main__":

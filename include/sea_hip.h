@@ -764,6 +764,26 @@ int sea_psp_add_relu(const float* a, const float* r, float* y, int64_t n, void* 
 int sea_psp_add_relu_bwd(const float* gy, const float* y, float* gx, int64_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * P4: the stem of PSPNet(clean=False), the torchvision-style ResNet-50 stem that takes an ImageNet-pre-trained backbone
+ * (backbones/resnet_ddcat.py:115-131: conv1 = Conv2d(3, 64, 7, stride 2, padding 3, bias=False), bn1, relu, maxpool =
+ * MaxPool2d(3, 2, 1); ddcat_psp.py:396-419: layer0 = Sequential(conv1, bn1, relu, maxpool)), for frozen parameters.  fp32
+ * FMA in a fixed order, no atomics: bitwise repeatable.  Finite inputs; any H, W >= 1.
+ * Hc = (H-1)/2 + 1, Hp = (Hc-1)/2 + 1 (W alike).
+ * sea_psp_stem_fwd: out = maxpool3x3s2p1(relu(scale[c] * conv7x7s2p3(x, w)[c] + shift[c])) in ONE launch; the pre-pool
+ *   map is never written.  x (B, 3, H, W) NCHW, w (64, 3, 7, 7), scale / shift (64): the folded eval BatchNorm, out
+ *   (B, Hp, Wp, 64) NHWC.  rec, if not NULL: (B, Hp, Wp, 64) bytes, the window position ky*3 + kx (0-8) of the largest
+ *   pre-activation, the first in row-major order among the positions inside the map (torch's choice), or 15 where that
+ *   value is <= 0 (out is 0 there and no gradient passes).  Every element of out / rec is written.
+ * sea_psp_stem_bwd: dx (B, 3, H, W) NCHW, the input gradient, as a gather: a pre-pool position belongs to at most 2 x 2
+ *   pool windows; its gradient is the sum (rows outer, columns inner) of dout of those whose rec names it, times scale[c];
+ *   dx is the transposed 7x7 stride-2 convolution of that.  Every element of dx is written (no zero-fill needed).
+ *   Replaces the backward of the same four modules and what they keep for it (the pre-pool map, ATen's int64 indices). */
+int sea_psp_stem_fwd(const float* x, const float* w, const float* scale, const float* shift, float* out,
+                     unsigned char* rec, int B, int H, int W, void* stream);
+int sea_psp_stem_bwd(const float* dout, const unsigned char* rec, const float* w, const float* scale, float* dx, int B,
+                     int H, int W, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * T1: train-mode BatchNorm2d of PSPNet-ResNet50's PIR-AT outer step (the reference trains every nn.BatchNorm2d of
  * backbones/resnet_ddcat.py and ddcat_psp.py on batch statistics: tools/train_rob_seg.py:338-340), fused with the ReLU or
  * residual-add + ReLU that follows it (resnet_ddcat.py:97-105; ddcat_psp.py:21, 441-446).  fp32, x dense NHWC = an

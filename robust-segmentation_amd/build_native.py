@@ -53,6 +53,7 @@ SOURCES = [
     ("msf_grad.hip", ["-ffp-contract=off"]),
     ("sw_kernels.hip", ["-ffp-contract=off"]),
     ("psp_kernels.hip", []),
+    ("psp_stem.hip", []),
     ("bn_train.hip", []),
     ("train_loss.hip", []),
     ("train_loss_up.hip", []),

@@ -123,6 +123,8 @@ _SIGS = {
     "sea_psp_upsample_ac_nhwc_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "sea_psp_add_relu": (_i, [_vp, _vp, _vp, _i64, _vp]),
     "sea_psp_add_relu_bwd": (_i, [_vp, _vp, _vp, _i64, _vp]),
+    "sea_psp_stem_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "sea_psp_stem_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "sea_bn_train_workspace_floats": (_i64, [_i64, _i]),
     "sea_bn_train_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _f, _f, _i, _vp]),
     "sea_bn_train_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _vp]),
@@ -961,6 +963,63 @@ def add_relu_backward(gy, y):
     gx = torch.empty_like(y)
     _check(lib().sea_psp_add_relu_bwd(_p(gy), _p(y), _p(gx), y.numel(), _stream()), "sea_psp_add_relu_bwd")
     return gx
+
+
+# ------------------------------------------------------------------------------------------------ P4 (PSPNet, clean=False)
+def psp_stem_size(H: int, W: int):
+    """(Hp, Wp) of the robust stem's output for an (H, W) image: a stride-2 convolution, then a stride-2 pool"""
+    return (((H - 1) // 2 + 1) - 1) // 2 + 1, (((W - 1) // 2 + 1) - 1) // 2 + 1
+
+
+def _psp_stem_args(x_like, weight, scale, what):
+    if (x_like.dim() != 4 or tuple(weight.shape) != (64, 3, 7, 7) or tuple(scale.shape) != (64,)
+            or x_like.shape[0] > 65535):
+        raise SeaNativeError(f"{what}: a 4-d batch of at most 65535 images, weight (64,3,7,7) and scale (64,) expected")
+
+
+def psp_stem(x, weight, scale, shift, want_rec: bool = True, out=None, rec=None):
+    """P4: max_pool2d(relu(scale[c] * conv2d(x, weight, stride 2, padding 3)[c] + shift[c]), 3, 2, 1) of x (B,3,H,W) NCHW in
+    one launch -> (out, rec).  out is (B,64,Hp,Wp) in channels_last memory; rec (None unless ``want_rec``) is the uint8
+    tensor of the same shape and memory order that ``psp_stem_backward`` reads: the winner's window position ky*3 + kx, 15
+    where nothing passes.  ``out`` / ``rec`` may be given (dense channels_last, every element is overwritten)."""
+    _dev(x, weight, scale, shift, out, rec)
+    _psp_stem_args(x, weight, scale, "psp_stem")
+    if x.shape[1] != 3 or tuple(shift.shape) != (64,):
+        raise SeaNativeError("psp_stem: x (B,3,H,W) and shift (64,) expected")
+    x = _f32c(x)
+    B, _, H, W = x.shape
+    Hp, Wp = psp_stem_size(H, W)
+    if out is None:
+        out = _empty_cl(B, 64, Hp, Wp, x.device)
+    elif tuple(out.shape) != (B, 64, Hp, Wp) or out.dtype != torch.float32 or cl_pixel_stride(out) != 64:
+        raise SeaNativeError("psp_stem: out must be a dense channels_last float32 (B,64,Hp,Wp) tensor")
+    if rec is None and want_rec:
+        rec = torch.empty((B, Hp, Wp, 64), dtype=torch.uint8, device=x.device).permute(0, 3, 1, 2)
+    if rec is not None and (tuple(rec.shape) != (B, 64, Hp, Wp) or rec.dtype != torch.uint8
+                            or not rec.permute(0, 2, 3, 1).is_contiguous()):
+        raise SeaNativeError("psp_stem: rec must be a dense channels_last uint8 (B,64,Hp,Wp) tensor")
+    _check(lib().sea_psp_stem_fwd(_p(x), _p(_f32c(weight)), _p(_f32c(scale)), _p(_f32c(shift)), _p(out), _p(rec), B, H, W,
+                                  _stream()), "sea_psp_stem_fwd")
+    return out, rec
+
+
+def psp_stem_backward(dout, rec, weight, scale, H: int, W: int, out=None):
+    """P4: the input gradient (B,3,H,W) NCHW of ``psp_stem`` given dout (B,64,Hp,Wp) in channels_last memory and the
+    forward's ``rec``; every element is written (``out``, if given, needs no zero-fill)"""
+    _dev(dout, rec, weight, scale, out)
+    _psp_stem_args(dout, weight, scale, "psp_stem_backward")
+    B = dout.shape[0]
+    if tuple(dout.shape) != (B, 64) + psp_stem_size(H, W) or dout.dtype != torch.float32 or cl_pixel_stride(dout) != 64:
+        raise SeaNativeError("psp_stem_backward: dout must be dense channels_last float32 (B,64,Hp,Wp) for this H, W")
+    if tuple(rec.shape) != tuple(dout.shape) or rec.dtype != torch.uint8 or not rec.permute(0, 2, 3, 1).is_contiguous():
+        raise SeaNativeError("psp_stem_backward: rec must be the forward's uint8 record")
+    if out is None:
+        out = torch.empty((B, 3, H, W), dtype=torch.float32, device=dout.device)
+    elif tuple(out.shape) != (B, 3, H, W):
+        raise SeaNativeError("psp_stem_backward: out must be (B,3,H,W)")
+    _check(lib().sea_psp_stem_bwd(_p(dout), _p(rec), _p(_f32c(weight)), _p(_f32c(scale)), _p(_f32c(out)), B, H, W,
+                                  _stream()), "sea_psp_stem_bwd")
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ T1 (PSPNet training)

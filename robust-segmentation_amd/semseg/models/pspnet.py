@@ -1,9 +1,14 @@
-"""PSPNet-ResNet50 (semseg/models/ddcat_psp.py:372-486 of the reference, with the ``clean=True`` deep-base ResNet-50 of
-backbones/resnet_ddcat.py:110-131): the VOC model of the reference's tools/infer.py (``eval(MODEL.NAME)(50, N_CLS)``,
-configs/voc_pspnet_cais.yaml) and the architecture of the DDC-AT / CAIS baselines.
+"""PSPNet-ResNet50 (semseg/models/ddcat_psp.py:372-486 of the reference, with the ResNet-50 of
+backbones/resnet_ddcat.py:110-131) in both of the reference's shapes.  ``clean=True`` has the deep-base stem (three 3x3
+convolutions): the VOC model of the reference's tools/infer.py (``eval(MODEL.NAME)(50, N_CLS)``,
+configs/voc_pspnet_cais.yaml) and the architecture of the DDC-AT / CAIS baselines.  ``clean=False`` has the
+torchvision-style stem (one 7x7 stride-2 convolution, ``layer1`` starting from 64 channels): the shape that takes a
+robustly pre-trained ImageNet ResNet-50, which the reference's trainer builds for every config whose ``ADDENDUM`` does
+not contain "clean" (tools/train_rob_seg.py:92-98), i.e. the PSPNet of PIR-AT.
 
-Same modules, names and state-dict keys as the reference (370 keys, ``aux.*`` included), so a reference checkpoint loads
-with ``strict=True``.  ``indicate == 1``, bf16 autocast and CPU tensors run the reference's forward on plain torch ops.  The
+Same modules, names and state-dict keys as the reference (370 keys for ``clean=True``, 358 for ``clean=False``, ``aux.*``
+included), so a reference checkpoint loads with ``strict=True``.  ``indicate == 1``, bf16 autocast and CPU tensors run the
+reference's forward on plain torch ops.  The
 frozen eval forward of a float32 device batch -- what SEA attacks -- and its input gradient run on the device kernels
 ("PSPNet"):
 
@@ -14,8 +19,10 @@ frozen eval forward of a float32 device batch -- what SEA attacks -- and its inp
 - the bottleneck's ``relu(bn3(conv3(.)) + identity)``: M8 with the folded bias, then P3;
 - PPM: the adaptive pool of M2'', M8, and P2 writing the align_corners=True up-sampling straight into the concatenation;
 - ``cls``: Winograd 4096 -> 512, then the M10 classifier GEMM (NCHW logits), then P2 (x8, align_corners=True).
-The stem's stride-2 3-input-channel convolution, layer2's stride-2 3x3 and the max-pool stay with the library (about 1 %
-of the FLOPs).  There is deliberately no ``forward_lowres`` hook: K2u and K10b assume align_corners=False.
+- the ``clean=False`` stem, convolution + BatchNorm + ReLU + max-pool: P4 (csrc/psp_stem.hip), one launch per direction, the
+  pre-pool map never written (``STEM_FUSED``, read once from ``SEA_PSP_STEM_FUSED``, default 1; 0 = the library line).
+The deep-base stem's stride-2 3-input-channel convolution and max-pool and layer2's stride-2 3x3 stay with the library
+(about 1 % of the FLOPs).  There is deliberately no ``forward_lowres`` hook: K2u and K10b assume align_corners=False.
 
 Training mode (PIR-AT's outer step, tools/train_rob_seg.py) of a float32 device batch keeps the reference's module order and
 return value ``(main_loss, aux_loss, x)``; every BatchNorm runs on T1 (train-mode statistics, running-buffer update and
@@ -46,6 +53,7 @@ USE_NATIVE = True
 _CL = torch.channels_last
 TRAIN_CRITERIA = ("torch", "native", "fused")
 TRAIN_CRITERION = os.environ.get("SEA_PSP_TRAIN_CRITERION", "").strip() or "torch"
+STEM_FUSED = os.environ.get("SEA_PSP_STEM_FUSED", "1").strip() != "0"     # P4 for the clean=False stem of the frozen model
 if TRAIN_CRITERION not in TRAIN_CRITERIA:
     raise ValueError(f"SEA_PSP_TRAIN_CRITERION must be one of {TRAIN_CRITERIA}, got {TRAIN_CRITERION!r}")
 
@@ -109,26 +117,29 @@ def _conv3x3(cin, cout, stride=1):
 
 class PSPNet(nn.Module):
     """``PSPNet(50, n_cls)`` of the reference (ddcat_psp.py:372-486).  ``pretrained`` is accepted and ignored (the
-    reference reads fixed cluster paths there); only ``layers=50`` with ``clean=True`` is built."""
+    reference reads fixed cluster paths there); only ``layers=50`` is built.  ``clean`` chooses the stem: the deep-base one
+    (True) or the torchvision-style one that a pre-trained ImageNet ResNet-50 fits (False: resnet_ddcat.py:115-131)."""
 
     def __init__(self, layers=50, classes=21, bins=(1, 2, 3, 6), dropout=0.1, zoom_factor=8, use_ppm=True,
                  criterion=nn.CrossEntropyLoss(ignore_index=-1), BatchNorm=nn.BatchNorm2d, pretrained=True, clean=True):
         super().__init__()
         if layers != 50:
             raise ValueError(f"PSPNet: only layers=50 is built here, got {layers}")
-        if not clean:
-            raise ValueError("PSPNet: only the clean=True deep-base ResNet-50 is built here")
         assert 2048 % len(bins) == 0
         assert classes > 1
         assert zoom_factor in [1, 2, 4, 8]
         self.zoom_factor = zoom_factor
         self.use_ppm = use_ppm
         self.criterion = criterion
-        self.layer0 = nn.Sequential(_conv3x3(3, 64, 2), BatchNorm(64), nn.ReLU(inplace=True),
-                                    _conv3x3(64, 64), BatchNorm(64), nn.ReLU(inplace=True),
-                                    _conv3x3(64, 128), BatchNorm(128), nn.ReLU(inplace=True),
-                                    nn.MaxPool2d(kernel_size=3, stride=2, padding=1))
-        self.layer1 = _make_layer(128, 64, 3, 1, BatchNorm)
+        if clean:
+            self.layer0 = nn.Sequential(_conv3x3(3, 64, 2), BatchNorm(64), nn.ReLU(inplace=True),
+                                        _conv3x3(64, 64), BatchNorm(64), nn.ReLU(inplace=True),
+                                        _conv3x3(64, 128), BatchNorm(128), nn.ReLU(inplace=True),
+                                        nn.MaxPool2d(kernel_size=3, stride=2, padding=1))
+        else:                                                           # ddcat_psp.py:418-419
+            self.layer0 = nn.Sequential(nn.Conv2d(3, 64, kernel_size=7, stride=2, padding=3, bias=False), BatchNorm(64),
+                                        nn.ReLU(inplace=True), nn.MaxPool2d(kernel_size=3, stride=2, padding=1))
+        self.layer1 = _make_layer(128 if clean else 64, 64, 3, 1, BatchNorm)
         self.layer2 = _make_layer(256, 128, 4, 2, BatchNorm)
         self.layer3 = _make_layer(512, 256, 6, 2, BatchNorm)
         self.layer4 = _make_layer(1024, 512, 3, 2, BatchNorm)
@@ -375,13 +386,49 @@ def _block(blk, x):
     return _AddRelu.apply(out, residual)
 
 
+class _RobustStem(torch.autograd.Function):
+    """P4: maxpool3x3s2p1(relu(scale * conv7x7s2p3(x, w) + shift)) of the NCHW image as one launch, channels_last result;
+    backward: the input gradient as a gather through the one-byte winner record (frozen weights: no other gradient)"""
+
+    @staticmethod
+    @_fp32_fwd
+    def forward(ctx, x, weight, scale, shift):
+        from .. import _native as N
+        out, rec = N.psp_stem(x.contiguous(), weight, scale, shift, want_rec=ctx.needs_input_grad[0])
+        ctx.size = tuple(x.shape[2:])
+        ctx.save_for_backward(rec, weight, scale)
+        return out
+
+    @staticmethod
+    @_fp32_bwd
+    def backward(ctx, g):
+        from .. import _native as N
+        rec, weight, scale = ctx.saved_tensors
+        return N.psp_stem_backward(_dense_cl(g), rec, weight, scale, *ctx.size), None, None, None
+
+
+def _robust_stem_ok(l0):
+    conv = l0[0]
+    return (tuple(conv.weight.shape) == (64, 3, 7, 7) and conv.stride == (2, 2) and conv.padding == (3, 3)
+            and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros"
+            and conv.weight.dtype == torch.float32 and conv.weight.is_contiguous() and isinstance(l0[3], nn.MaxPool2d)
+            and (l0[3].kernel_size, l0[3].stride, l0[3].padding, l0[3].dilation, l0[3].ceil_mode) == (3, 2, 1, 1, False))
+
+
 def _native_forward(model, x, size):
     l0 = model.layer0
-    x = x.contiguous(memory_format=_CL)
-    x = F.relu(l0[1](l0[0](x)))                     # stride 2, 3 input channels: the library (MIOpen)
-    x = _conv3x3_bn_relu(l0[3], l0[4], x)
-    x = _conv3x3_bn_relu(l0[6], l0[7], x)
-    x = _dense_cl(l0[9](x))
+    if len(l0) == 4:                                # clean=False: conv7x7 s2, bn, relu, maxpool
+        if STEM_FUSED and _robust_stem_ok(l0):
+            scale, shift = _folded_bn(l0[1], l0[0].bias, _cache(l0[0]))
+            x = _RobustStem.apply(x, l0[0].weight, scale, shift)
+        else:
+            x = _dense_cl(l0[3](F.relu(l0[1](l0[0](x.contiguous(memory_format=_CL))))))
+    else:
+        x = x.contiguous(memory_format=_CL)
+        x = F.relu(l0[1](l0[0](x)))                 # stride 2, 3 input channels: the library (MIOpen)
+        x = _conv3x3_bn_relu(l0[3], l0[4], x)
+        x = _conv3x3_bn_relu(l0[6], l0[7], x)
+        x = _dense_cl(l0[9](x))
     for layer in (model.layer1, model.layer2, model.layer3, model.layer4):
         for blk in layer:
             x = _block(blk, x)
@@ -479,9 +526,12 @@ def _native_train_forward(model, x, y, size):
     l0 = model.layer0
     x = x.contiguous(memory_format=_CL)
     x = _bn_train(l0[1], l0[0](x), True)
-    x = _bn_train(l0[4], _conv_train(l0[3], x), True)
-    x = _bn_train(l0[7], _conv_train(l0[6], x), True)
-    x = l0[9](x)
+    if len(l0) == 4:                                # clean=False: library convolution (weight gradient), T1, library pool
+        x = l0[3](x)
+    else:
+        x = _bn_train(l0[4], _conv_train(l0[3], x), True)
+        x = _bn_train(l0[7], _conv_train(l0[6], x), True)
+        x = l0[9](x)
     for layer in (model.layer1, model.layer2, model.layer3):
         for blk in layer:
             x = _block_train(blk, x)

@@ -22,6 +22,11 @@ loss-wise_miou, `argmax-logs/{model}_{loss}_{eps}.pt` = ONE (N,H,W) int64 tensor
 
 Like the reference, the three standard SEA losses always run; `--attack X` (which the reference parses and then
 overwrites, tools/infer.py:332-336) restricts the run to that one loss here and every table is sized for it.
+
+A PSPNet config may carry the optional key ``MODEL.CLEAN``: absent or true builds ``PSPNet(50, N_CLS)`` with the deep-base
+stem, false builds ``PSPNet(50, N_CLS, clean=False)``, the torchvision-style stem of PIR-AT's pre-trained backbone
+(configs/pascalvoc_pspnet_pirat.yaml).  Absent means true so that configs/pascalvoc_pspnet.yaml evaluates what it always
+did; the reference's trainer would read that file's ``ADDENDUM: run`` as ``clean=False`` (tools/train_rob_seg.py:92-98).
 """
 from __future__ import annotations
 
@@ -189,7 +194,11 @@ def build_model(cfg, random_init: bool, device):
         model = create_segmenter(mcfg, None, test_cfg["BACKBONE"])
     elif model_cfg["NAME"] == "PSPNet":
         from semseg.models import PSPNet
-        model = PSPNet(50, test_cfg["N_CLS"])            # the reference's eval(MODEL.NAME)(50, N_CLS) (tools/infer.py:266-268)
+        clean = model_cfg.get("CLEAN", True)
+        if not isinstance(clean, bool):
+            raise ValueError(f"MODEL.CLEAN must be true or false, got {clean!r}")
+        # the reference's eval(MODEL.NAME)(50, N_CLS) (tools/infer.py:266-268); MODEL.CLEAN: false = the robust 7x7 stem
+        model = PSPNet(50, test_cfg["N_CLS"], clean=clean)
     else:
         raise ValueError(f"model family {model_cfg['NAME']} is outside this build (SURVEY 2.1)")
     if not random_init:

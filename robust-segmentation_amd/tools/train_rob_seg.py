@@ -20,7 +20,12 @@ Optimizer param groups and the warm-up + polynomial LR schedule follow semseg/op
 semseg/schedulers.py:80-134.  PSPNet (configs/pascalvoc_pspnet.yaml) follows the reference's own recipe instead
 (tools/train_rob_seg.py:92-98, 185-204, 338-361): ``PSPNet(50, N_CLS)``, loss = main_loss + 0.4 * aux_loss, SGD over eight
 parameter groups (layer0-4, then ppm, cls, aux) and the poly rule set after every step, x10 on the new modules, with no
-warm-up (SCHEDULER is ignored).  Its crops satisfy (H - 1) % 8 == 0.
+warm-up (SCHEDULER is ignored).  Its crops satisfy (H - 1) % 8 == 0.  The optional key ``MODEL.CLEAN`` chooses the
+backbone's stem: absent or true builds ``PSPNet(50, N_CLS)`` (the deep-base stem, ``clean=True``), false builds
+``PSPNet(50, N_CLS, clean=False)``, the torchvision-style stem that takes a pre-trained ImageNet ResNet-50
+(configs/pascalvoc_pspnet_pirat.yaml).  The reference decides this from the config's ``ADDENDUM`` instead
+(tools/train_rob_seg.py:92-98: clean unless the word "clean" is missing) and would read configs/pascalvoc_pspnet.yaml's
+``ADDENDUM: run`` as ``clean=False``; here that file keeps building the deep-base model.
 ``--native-blocks`` runs the fp32 outer step's ConvNeXt trunk in NHWC on libsea_hip for this run (T3: LayerNorm with
 parameter gradients, fused stochastic-depth tail; ``semseg.models.convnext_upernet.TRAIN_NATIVE_BLOCKS``).
 ``--fused-criterion`` fuses the UperNet branch's final up-sampling into its two cross-entropies for this run (T2u;
@@ -54,6 +59,14 @@ from semseg.models import convnext_upernet as _convnext  # noqa: E402
 from semseg.models import pspnet as _pspnet  # noqa: E402
 from semseg.models import PSPNet, UperNetForSemanticSegmentation, create_segmenter  # noqa: E402
 from semseg.val import Pgd_Attack, Pgd_Attack_1  # noqa: E402
+
+
+def psp_clean(model_cfg) -> bool:
+    """``MODEL.CLEAN`` of a PSPNet config: absent means true (the deep-base stem); false is the robust 7x7 stem"""
+    clean = model_cfg.get("CLEAN", True)
+    if not isinstance(clean, bool):
+        raise ValueError(f"MODEL.CLEAN must be true or false, got {clean!r}")
+    return clean
 
 
 def group_weight(model):
@@ -221,7 +234,7 @@ def _main(argv=None):
         mcfg, _ = load_config_segmenter(backbone=model_cfg["BACKBONE"], n_cls=C)
         model = create_segmenter(mcfg, None, model_cfg["BACKBONE"])
     elif model_cfg["NAME"] == "PSPNet":
-        model = PSPNet(50, C)
+        model = PSPNet(50, C, clean=psp_clean(model_cfg))
     else:
         raise ValueError(model_cfg["NAME"])
     psp = model_cfg["NAME"] == "PSPNet"
