@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""Milliseconds per APGD step on PSPNet-ResNet50 (mask-ce-bal, Linf, random-init weights), device path against the stock
-PyTorch-ROCm forward / backward of the same module (pspnet.USE_NATIVE = False):
+"""Milliseconds per APGD step on PSPNet-ResNet50 or DeepLabV3-ResNet50 (mask-ce-bal, Linf, random-init weights), device
+path against the stock PyTorch-ROCm forward / backward of the same module (``USE_NATIVE = False`` in the model's module):
 
-    python devtools/psp_bench.py [--batch 8] [--size 473] [--classes 21] [--steps 10] [--warmup 3] [--graph 1]
-                                 [--clean 1] [--stem fused] [--windows 0]
+    python devtools/psp_bench.py [--model pspnet] [--batch 8] [--size 473] [--classes 21] [--steps 10] [--warmup 3]
+                                 [--graph 1] [--clean 1] [--stem fused] [--windows 0]
 
 Prints one JSON line per mode, with the model-side roofline line: about 0.3 TFLOP per 473 x 473 image for the forward
 (cls 3x3 0.14, layer4 0.10, layer3 0.05) and about the same again for the input gradient.
@@ -14,7 +14,10 @@ the configurations -- ``native`` with the fused stem, ``native`` with the librar
 model and their own attack run, and alternate inside one process: N windows each of ``--steps`` attack steps between two
 device events, median / fastest / slowest window; then the stem alone (forward + input gradient of ``layer0``, fused and
 library alternating, N windows of ``--stem-iters`` passes) with the peak allocation of one pass above the inputs.  A ``#``
-header line, then one JSON line per part."""
+header line, then one JSON line per part.
+
+``--model deeplabv3`` builds ``DeepLabV3(50, classes=C)``; with ``--windows N`` its two configurations, ``native`` and
+``stock``, alternate in one process in the same way (median / fastest / slowest window)."""
 import argparse
 import copy
 import json
@@ -47,6 +50,7 @@ def _flops_per_image(model, size):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--model", type=str, default="pspnet", choices=("pspnet", "deeplabv3"))
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--size", type=int, default=473)
     ap.add_argument("--classes", type=int, default=21)
@@ -61,14 +65,21 @@ def main():
     args = ap.parse_args()
 
     from semseg import attacker as A
-    from semseg.models import PSPNet, pspnet
+    from semseg.models import DeepLabV3, PSPNet, deeplabv3, pspnet
     from semseg.utils.utils import VOC_WTS
 
     B, S, C = args.batch, args.size, args.classes
     clean = bool(args.clean)
-    flops = _flops_per_image(PSPNet(50, C, clean=clean).eval(), S)
+    deeplab = args.model == "deeplabv3"
+    switch = deeplabv3 if deeplab else pspnet          # the module whose USE_NATIVE chooses the path
+    name = "DeepLabV3_RN50" if deeplab else "PSPNet_RN50"
+
+    def build():
+        return DeepLabV3(50, classes=C) if deeplab else PSPNet(50, C, clean=clean)
+
+    flops = _flops_per_image(build().eval(), S)
     torch.manual_seed(0)
-    model = PSPNet(50, C, clean=clean).eval().cuda()
+    model = build().eval().cuda()
     for p in model.parameters():
         p.requires_grad_(False)
     x = torch.rand(B, 3, S, S, generator=torch.Generator().manual_seed(1)).cuda()
@@ -76,12 +87,14 @@ def main():
         y = model(x).max(1)[1]
     w = torch.tensor(VOC_WTS, device="cuda")[:C] if C == 21 else torch.ones(C, device="cuda")
     A.USE_HIP_GRAPH = bool(args.graph)
+    if args.windows > 0 and deeplab:
+        return _ab_paths(args, model, x, y, w, flops, switch, name)
     if args.windows > 0:
         assert not clean, "--windows is the A/B of the clean=False stem"
         return _ab(args, model, x, y, w, flops)
     pspnet.STEM_FUSED = args.stem == "fused"
     for mode in args.modes.split(","):
-        pspnet.USE_NATIVE = mode == "native"
+        switch.USE_NATIVE = mode == "native"
         A.release_graph_cache(model)
         W, K = args.warmup, args.steps
         run = A.ApgdRun(model, x, y, 8.0 / 255, max(W + K + 1, A.GRAPH_MIN_ITER), "mask-ce-bal", "ce-avg", True, C, w,
@@ -96,12 +109,55 @@ def main():
         torch.cuda.synchronize()
         ms = (time.perf_counter() - t0) * 1e3 / K
         tflops = 2 * flops * B / (ms * 1e-3) / 1e12      # forward + input gradient
-        print(json.dumps({"model": "PSPNet_RN50", "mode": mode, "clean": clean, "stem": args.stem, "B": B, "size": S,
+        print(json.dumps({"model": name, "mode": mode, "clean": clean, "stem": args.stem, "B": B, "size": S,
                           "classes": C, "graph": bool(args.graph),
                           "ms_per_step": round(ms, 3), "fwd_tflop_per_image": round(flops / 1e12, 4),
                           "model_tflops": round(tflops, 1)}), flush=True)
-    pspnet.USE_NATIVE = True
+    switch.USE_NATIVE = True
     A.release_graph_cache(model)
+
+
+def _ab_paths(args, model, x, y, w, flops, switch, name):
+    """device path against stock path of one model: a model copy and an attack run each, alternating windows"""
+    from semseg import attacker as A
+    B, S, C, K, W, NW = args.batch, args.size, args.classes, args.steps, max(args.warmup, 3), args.windows
+    print(f"# devtools/psp_bench.py --model {args.model} --windows {NW}: {name}, random weights, B = {B}, {S}^2, fp32, "
+          f"graph = {bool(args.graph)}; ms per APGD step (mask-ce-bal, Linf), median / fastest / slowest of {NW} windows of "
+          f"{K} steps, native (device path) and stock (USE_NATIVE = False) alternating in one process (a model copy and "
+          "an attack run each)", flush=True)
+    configs = {"native": True, "stock": False}
+    runs = {}
+    for cfg, on in configs.items():
+        switch.USE_NATIVE = on
+        m = copy.deepcopy(model)
+        run = A.ApgdRun(m, x, y, 8.0 / 255, max(W + NW * K + 1, A.GRAPH_MIN_ITER), "mask-ce-bal", "ce-avg", True, C, w,
+                        x.clone())
+        run.start()
+        for i in range(W):
+            run.step(i)
+        runs[cfg] = (m, run)
+    times = {cfg: [] for cfg in configs}
+    for k in range(NW):
+        for cfg, (m, run) in runs.items():
+            switch.USE_NATIVE = configs[cfg]
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for i in range(W + k * K, W + (k + 1) * K):
+                run.step(i)
+            e1.record()
+            torch.cuda.synchronize()
+            times[cfg].append(e0.elapsed_time(e1) / K)
+    row = dict(part="apgd_step", model=name, B=B, size=S, classes=C, graph=bool(args.graph), windows=NW, steps=K,
+               fwd_tflop_per_image=round(flops / 1e12, 4))
+    for cfg in configs:
+        row[cfg] = _summary(times[cfg])
+    row["stock_over_native"] = round(row["stock"]["median_ms"] / row["native"]["median_ms"], 4)
+    row["peak_GB"] = round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)
+    print(json.dumps(row), flush=True)
+    for m, run in runs.values():
+        A.release_graph_cache(m)
+    switch.USE_NATIVE = True
 
 
 def _summary(ts):

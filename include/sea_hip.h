@@ -784,6 +784,28 @@ int sea_psp_stem_bwd(const float* dout, const unsigned char* rec, const float* w
                      int H, int W, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * P5: the dilated 3x3 branches of DeepLabV3's ASPP (ddcat_psp.py:44-58: Conv2d(in, out, 3, padding=rate, dilation=rate,
+ * bias=False), BatchNorm, ReLU; ddcat_psp.py:69-81: their concatenation) for frozen parameters, as "product first, shift
+ * second": Z = X . W_all^T on the un-shifted map (one M8 product; row (9 r + t) Cb + c of W_all = BatchNorm scale[c] *
+ * weight_r[c][:][ky][kx], t = 3 ky + kx), then a 9-tap gather of Cb-channel rows.  fp32 NHWC rows, 64-bit element
+ * offsets, one float4 per lane, no atomics: bitwise repeatable.
+ * Every tensor is (B, H, W, .) rows with its own pixel stride ld (a multiple of 4) and first column col0 (a multiple of
+ * 4) behind a 16-byte aligned base; R branches (1 <= R <= 4), rates[r] >= 1 (host array of R ints, read during the
+ * call), Cb % 4 == 0.  Z's columns [z_col0, z_col0 + 9 R Cb) and Y's [y_col0, y_col0 + R Cb) must lie inside a pixel.
+ * sea_aspp_tap_sum: Y[b][y][x][y_col0 + r Cb + c] = max(acc + shift[r Cb + c], 0) with acc = 0.f, then, for t = 0 .. 8
+ *   in that order, acc += Z[b][y + (ky-1) rate_r][x + (kx-1) rate_r][z_col0 + (9 r + t) Cb + c]; a tap whose source
+ *   pixel lies outside the map is skipped.  shift: R Cb floats (the folded BatchNorm shift).  Compiled without
+ *   contraction: the bits are those of the written-out sum.  Nothing outside Y's R Cb columns is written.
+ * sea_aspp_tap_sum_backward: dZ[b][y'][x'][z_col0 + (9 r + t) Cb + c] = Y[q] > 0 ? dY[q] : 0 at q = (y' - (ky-1) rate_r,
+ *   x' - (kx-1) rate_r), 0 where q lies outside the map: a gather that writes every element of dZ's 9 R Cb columns
+ *   exactly once, zeros included.  y: the forward's saved output (the ReLU gate, as sea_psp_add_relu_bwd). */
+int sea_aspp_tap_sum(const float* z, int64_t ldz, int64_t z_col0, const float* shift, float* y, int64_t ldy,
+                     int64_t y_col0, int B, int H, int W, int R, int Cb, const int* rates, void* stream);
+int sea_aspp_tap_sum_backward(const float* dy, int64_t lddy, int64_t dy_col0, const float* y, int64_t ldy,
+                              int64_t y_col0, float* dz, int64_t ldz, int64_t z_col0, int B, int H, int W, int R, int Cb,
+                              const int* rates, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * T1: train-mode BatchNorm2d of PSPNet-ResNet50's PIR-AT outer step (the reference trains every nn.BatchNorm2d of
  * backbones/resnet_ddcat.py and ddcat_psp.py on batch statistics: tools/train_rob_seg.py:338-340), fused with the ReLU or
  * residual-add + ReLU that follows it (resnet_ddcat.py:97-105; ddcat_psp.py:21, 441-446).  fp32, x dense NHWC = an

@@ -54,6 +54,7 @@ SOURCES = [
     ("sw_kernels.hip", ["-ffp-contract=off"]),
     ("psp_kernels.hip", []),
     ("psp_stem.hip", []),
+    ("aspp_kernels.hip", ["-ffp-contract=off"]),
     ("bn_train.hip", []),
     ("train_loss.hip", []),
     ("train_loss_up.hip", []),

@@ -125,6 +125,9 @@ _SIGS = {
     "sea_psp_add_relu_bwd": (_i, [_vp, _vp, _vp, _i64, _vp]),
     "sea_psp_stem_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "sea_psp_stem_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "sea_aspp_tap_sum": (_i, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, C.POINTER(C.c_int), _vp]),
+    "sea_aspp_tap_sum_backward": (_i, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i, _i, _i, _i, _i,
+                                       C.POINTER(C.c_int), _vp]),
     "sea_bn_train_workspace_floats": (_i64, [_i64, _i]),
     "sea_bn_train_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _f, _f, _i, _vp]),
     "sea_bn_train_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _vp]),
@@ -1020,6 +1023,82 @@ def psp_stem_backward(dout, rec, weight, scale, H: int, W: int, out=None):
     _check(lib().sea_psp_stem_bwd(_p(dout), _p(rec), _p(_f32c(weight)), _p(_f32c(scale)), _p(_f32c(out)), B, H, W,
                                   _stream()), "sea_psp_stem_bwd")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ P5 (DeepLabV3's ASPP)
+ASPP_MAX_BRANCHES = 4
+
+
+def _aspp_rows(t, what):
+    """(B, H, W, ld) float32 rows, dense"""
+    if t.dim() != 4 or t.dtype != torch.float32 or not t.is_contiguous():
+        raise SeaNativeError(f"{what}: a contiguous float32 (B, H, W, columns) tensor expected")
+    return t
+
+
+def _aspp_slice(t, B, Cc, H, W, what):
+    """pixel stride of a (B, Cc, H, W) channels_last tensor or channel slice of one"""
+    S = cl_pixel_stride(t)
+    if tuple(t.shape) != (B, Cc, H, W) or S is None:
+        raise SeaNativeError(f"{what}: a ({B},{Cc},{H},{W}) channels_last float32 tensor or a channel slice of one expected")
+    return S
+
+
+def _aspp_rates(rates):
+    rates = tuple(int(r) for r in rates)
+    return rates, (C.c_int * len(rates))(*rates)
+
+
+def aspp_tap_sum(z, rates, shift, out=None, Cb: Optional[int] = None, z_col0: int = 0):
+    """P5: the R = len(rates) dilated 3x3 branches of an ASPP from the un-shifted product ``z`` (B, H, W, ldz), whose column
+    ``z_col0 + (9 r + t) Cb + c`` holds tap t = 3 ky + kx of branch r: relu(shift[r Cb + c] + sum over the taps inside the
+    map, in order, of z at the pixel shifted by ((ky-1) rate_r, (kx-1) rate_r)).  ``shift``: (R * Cb,).  ``out``: a
+    (B, R * Cb, H, W) channels_last tensor or a channel slice of a wider one (written in place)."""
+    _dev(z, shift, out)
+    _aspp_rows(z, "aspp_tap_sum")
+    B, H, W, ldz = z.shape
+    rates, arr = _aspp_rates(rates)
+    R = len(rates)
+    if Cb is None:
+        Cb = shift.numel() // max(R, 1)
+    shift = _f32c(shift)
+    if shift.numel() != R * Cb:
+        raise SeaNativeError(f"aspp_tap_sum: shift must hold {R} x {Cb} floats")
+    if out is None:
+        out = _empty_cl(B, R * Cb, H, W, z.device)
+    S = _aspp_slice(out, B, R * Cb, H, W, "aspp_tap_sum: out")
+    _check(lib().sea_aspp_tap_sum(_p(z), ldz, int(z_col0), _p(shift), _p(out), S, 0, B, H, W, R, int(Cb), arr, _stream()),
+           "sea_aspp_tap_sum")
+    return out
+
+
+def aspp_tap_sum_backward(gy, y, rates, z_col0: int = 0, out=None):
+    """P5: the gradient of ``aspp_tap_sum`` with respect to ``z``, (B, H, W, ldz): column ``z_col0 + (9 r + t) Cb + c`` of
+    pixel p is gy gated by y > 0 at the pixel p - ((ky-1) rate_r, (kx-1) rate_r), and 0 where that lies outside the map.
+    ``gy`` / ``y``: (B, R * Cb, H, W) channels_last tensors or channel slices (``y`` = the forward's output).  Every element of
+    the 9 R Cb branch columns is written, no other; ``out``: a contiguous (B, H, W, ldz) tensor to write them into
+    (default: a new one of exactly z_col0 + 9 R Cb columns)."""
+    _dev(gy, y)
+    if gy.dim() != 4 or gy.shape != y.shape:
+        raise SeaNativeError("aspp_tap_sum_backward: gy must have y's shape")
+    B, Cc, H, W = y.shape
+    rates, arr = _aspp_rates(rates)
+    R = len(rates)
+    if R < 1 or Cc % R:
+        raise SeaNativeError(f"aspp_tap_sum_backward: {Cc} channels are not {R} branches")
+    Cb = Cc // R
+    Sg = _aspp_slice(gy, B, Cc, H, W, "aspp_tap_sum_backward: gy")
+    Sy = _aspp_slice(y, B, Cc, H, W, "aspp_tap_sum_backward: y")
+    if out is None:
+        out = torch.empty((B, H, W, 9 * Cc + int(z_col0)), dtype=torch.float32, device=y.device)
+    _dev(out)
+    dz = _aspp_rows(out, "aspp_tap_sum_backward: out")
+    if tuple(dz.shape[:3]) != (B, H, W):
+        raise SeaNativeError(f"aspp_tap_sum_backward: out must be ({B}, {H}, {W}, columns)")
+    ldz = dz.shape[3]
+    _check(lib().sea_aspp_tap_sum_backward(_p(gy), Sg, 0, _p(y), Sy, 0, _p(dz), ldz, int(z_col0), B, H, W, R, Cb, arr,
+                                           _stream()), "sea_aspp_tap_sum_backward")
+    return dz
 
 
 # ------------------------------------------------------------------------------------------------ T1 (PSPNet training)

@@ -115,6 +115,39 @@ def _conv3x3(cin, cout, stride=1):
     return nn.Conv2d(cin, cout, kernel_size=3, stride=stride, padding=1, bias=False)
 
 
+def _build_backbone(model, BatchNorm, clean):
+    """``layer0`` .. ``layer4`` of the reference's dilated ResNet-50 as children of ``model`` (which must have no other
+    child yet: the initialisation walks ``model.modules()``), output stride 8"""
+    if clean:
+        model.layer0 = nn.Sequential(_conv3x3(3, 64, 2), BatchNorm(64), nn.ReLU(inplace=True),
+                                    _conv3x3(64, 64), BatchNorm(64), nn.ReLU(inplace=True),
+                                    _conv3x3(64, 128), BatchNorm(128), nn.ReLU(inplace=True),
+                                    nn.MaxPool2d(kernel_size=3, stride=2, padding=1))
+    else:                                                           # ddcat_psp.py:418-419
+        model.layer0 = nn.Sequential(nn.Conv2d(3, 64, kernel_size=7, stride=2, padding=3, bias=False), BatchNorm(64),
+                                    nn.ReLU(inplace=True), nn.MaxPool2d(kernel_size=3, stride=2, padding=1))
+    model.layer1 = _make_layer(128 if clean else 64, 64, 3, 1, BatchNorm)
+    model.layer2 = _make_layer(256, 128, 4, 2, BatchNorm)
+    model.layer3 = _make_layer(512, 256, 6, 2, BatchNorm)
+    model.layer4 = _make_layer(1024, 512, 3, 2, BatchNorm)
+    for m in model.modules():                                        # resnet_ddcat.py:139-144
+        if isinstance(m, nn.Conv2d):
+            nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+        elif isinstance(m, BatchNorm):
+            nn.init.constant_(m.weight, 1)
+            nn.init.constant_(m.bias, 0)
+    for n, m in model.layer3.named_modules():                        # ddcat_psp.py:429-438
+        if "conv2" in n:
+            m.dilation, m.padding, m.stride = (2, 2), (2, 2), (1, 1)
+        elif "downsample.0" in n:
+            m.stride = (1, 1)
+    for n, m in model.layer4.named_modules():
+        if "conv2" in n:
+            m.dilation, m.padding, m.stride = (4, 4), (4, 4), (1, 1)
+        elif "downsample.0" in n:
+            m.stride = (1, 1)
+
+
 class PSPNet(nn.Module):
     """``PSPNet(50, n_cls)`` of the reference (ddcat_psp.py:372-486).  ``pretrained`` is accepted and ignored (the
     reference reads fixed cluster paths there); only ``layers=50`` is built.  ``clean`` chooses the stem: the deep-base one
@@ -131,34 +164,7 @@ class PSPNet(nn.Module):
         self.zoom_factor = zoom_factor
         self.use_ppm = use_ppm
         self.criterion = criterion
-        if clean:
-            self.layer0 = nn.Sequential(_conv3x3(3, 64, 2), BatchNorm(64), nn.ReLU(inplace=True),
-                                        _conv3x3(64, 64), BatchNorm(64), nn.ReLU(inplace=True),
-                                        _conv3x3(64, 128), BatchNorm(128), nn.ReLU(inplace=True),
-                                        nn.MaxPool2d(kernel_size=3, stride=2, padding=1))
-        else:                                                           # ddcat_psp.py:418-419
-            self.layer0 = nn.Sequential(nn.Conv2d(3, 64, kernel_size=7, stride=2, padding=3, bias=False), BatchNorm(64),
-                                        nn.ReLU(inplace=True), nn.MaxPool2d(kernel_size=3, stride=2, padding=1))
-        self.layer1 = _make_layer(128 if clean else 64, 64, 3, 1, BatchNorm)
-        self.layer2 = _make_layer(256, 128, 4, 2, BatchNorm)
-        self.layer3 = _make_layer(512, 256, 6, 2, BatchNorm)
-        self.layer4 = _make_layer(1024, 512, 3, 2, BatchNorm)
-        for m in self.modules():                                        # resnet_ddcat.py:139-144
-            if isinstance(m, nn.Conv2d):
-                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
-            elif isinstance(m, BatchNorm):
-                nn.init.constant_(m.weight, 1)
-                nn.init.constant_(m.bias, 0)
-        for n, m in self.layer3.named_modules():                        # ddcat_psp.py:429-438
-            if "conv2" in n:
-                m.dilation, m.padding, m.stride = (2, 2), (2, 2), (1, 1)
-            elif "downsample.0" in n:
-                m.stride = (1, 1)
-        for n, m in self.layer4.named_modules():
-            if "conv2" in n:
-                m.dilation, m.padding, m.stride = (4, 4), (4, 4), (1, 1)
-            elif "downsample.0" in n:
-                m.stride = (1, 1)
+        _build_backbone(self, BatchNorm, clean)
         fea_dim = 2048
         if use_ppm:
             self.ppm = PPM(fea_dim, int(fea_dim / len(bins)), bins, BatchNorm)
@@ -415,7 +421,9 @@ def _robust_stem_ok(l0):
             and (l0[3].kernel_size, l0[3].stride, l0[3].padding, l0[3].dilation, l0[3].ceil_mode) == (3, 2, 1, 1, False))
 
 
-def _native_forward(model, x, size):
+def _native_backbone(model, x):
+    """``layer0`` .. ``layer4`` of the frozen dilated ResNet-50 on the device path (shared with DeepLabV3, whose backbone
+    is this one layer for layer): (layer4's output, layer3's output), dense channels_last"""
     l0 = model.layer0
     if len(l0) == 4:                                # clean=False: conv7x7 s2, bn, relu, maxpool
         if STEM_FUSED and _robust_stem_ok(l0):
@@ -429,9 +437,17 @@ def _native_forward(model, x, size):
         x = _conv3x3_bn_relu(l0[3], l0[4], x)
         x = _conv3x3_bn_relu(l0[6], l0[7], x)
         x = _dense_cl(l0[9](x))
-    for layer in (model.layer1, model.layer2, model.layer3, model.layer4):
+    for layer in (model.layer1, model.layer2, model.layer3):
         for blk in layer:
             x = _block(blk, x)
+    x_tmp = x
+    for blk in model.layer4:
+        x = _block(blk, x)
+    return x, x_tmp
+
+
+def _native_forward(model, x, size):
+    x, _ = _native_backbone(model, x)
     if model.use_ppm:
         branches = [_pointwise(f[1], f[2], _adaptive_pool(f[0], x), True) for f in model.ppm.features]
         x = _UpCatAC.apply(tuple(x.shape[2:]), x, *branches)

@@ -85,6 +85,8 @@ def getModelName(mname, backname):
         return "SegMent_" + backname
     if mname == "UperNetForSemanticSegmentation":
         return "UperNet_" + backname
+    if mname == "DeepLabV3":
+        return "DeepLabV3_RN50"
     return "PSPNet_RN50"
 
 

@@ -199,6 +199,10 @@ def build_model(cfg, random_init: bool, device):
             raise ValueError(f"MODEL.CLEAN must be true or false, got {clean!r}")
         # the reference's eval(MODEL.NAME)(50, N_CLS) (tools/infer.py:266-268); MODEL.CLEAN: false = the robust 7x7 stem
         model = PSPNet(50, test_cfg["N_CLS"], clean=clean)
+    elif model_cfg["NAME"] == "DeepLabV3":
+        from semseg.models import DeepLabV3
+        # by keyword: the second positional parameter of the reference's DeepLabV3 is atrous_rates (ddcat_psp.py:85-96)
+        model = DeepLabV3(50, classes=test_cfg["N_CLS"])
     else:
         raise ValueError(f"model family {model_cfg['NAME']} is outside this build (SURVEY 2.1)")
     if not random_init:
